@@ -2,8 +2,24 @@
 """Benchmark: Mrays/s of the MI355X path-tracing megakernel on BASELINE.json's
 headline workload (config 2: book-cover scene, seed 2, 1280x720, r=64, d=50).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c4|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does only what the headline figure needs: it uploads the scene,
+renders the warmup frames, times the K steps, writes the last step's frame when
+--dump-outputs is given, and prints the JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, the configuration and the launch plan).
+Everything else this benchmark measures or checks (see "With --full" below)
+takes launches, renders or host work of its own and runs only with --full.
+
+--dump-outputs DIR writes, after the timed steps, DIR/frame.npy: the frame the
+LAST timed step rendered (progressive pass W + K - 1), float32 [rows, width, 3]
+linear RGB exactly as the timed launch left it in its output buffer (at N > 1
+the frame rank 0 assembled from the timed run's own gather). A frame larger
+than 64 MB (C3, C4) is written as a fixed sample of its rows (seeded, sorted;
+the same rows in every run). The scene, camera, seed and pass indices depend
+on the arguments alone, so two builds run with the same arguments can be
+compared frame for frame.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py launches its
 own N ranks (one child process per GPU, started before this process touches
@@ -32,7 +48,9 @@ records -; default 2), so a launch's
 workgroups start on the CUs the previous launch's last long paths leave idle.
 Every step still renders its whole frame inside the timed region.
 
-Also reported (rank 0):
+With --full, also measured and reported (rank 0; each takes untimed launches,
+renders or host work of its own, after the timed steps unless stated;
+--no-cpu-baseline, --no-e2e and --no-single drop single legs of it):
   roofline     the megakernel against the FP64 VALU roof (it is compute and
                latency bound; HBM traffic, by PMC, is far below its roof and is
                reported against the algorithmic W*H*12 B per frame): achieved = algorithmic VALU work per launch / mean
@@ -242,7 +260,14 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--tile-rows", type=int, default=1, help="rows per interleaved tile (N > 1): 1 balances best")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the roofline (instrumented "
+                         "launches), single-launch and per-rank timings, the drop-in call (e2e), the CPU baseline and "
+                         "the parity of the frame against the oracle. Off: set up, warm up, time the steps, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write DIR/frame.npy: the frame the last timed step rendered, float32 "
+                         "[rows, width, 3] (rank 0; above 64 MB a fixed seeded sample of its rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle's render and the parity")
     ap.add_argument("--no-e2e", action="store_true", help="skip the synchronous tray_render (drop-in) timings")
     ap.add_argument("--no-single", action="store_true", help="skip the one-frame launch timing (profiling runs)")
     ap.add_argument("--cpu-row-step", type=int, default=0,
@@ -265,6 +290,8 @@ def main() -> int:
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # No launcher: start the N ranks here, before anything touches the GPU.
         # The ranks' watchdogs bound each phase; this bounds the whole run as a backstop.
@@ -370,7 +397,9 @@ def main() -> int:
             scene.render_passes_async(cam._state, p, n, outs[k].data_ptr(), streams[k].cuda_stream)
 
     def frames(first, count):
+        """Render frames first .. first + count - 1; returns (slot, frames) of the last launch."""
         j = 0
+        k = n = 0
         for i in range(first, first + count, F):
             n = min(F, first + count - i)
             k = j % nslot
@@ -385,11 +414,12 @@ def main() -> int:
                     gathered[k] = torch.cuda.Event()
                     gathered[k].record(comm)
             j += 1
+        return k, n
 
-    # Untimed instrumented launches: segments, ray-sphere and ray-box tests for the
+    # --full: untimed instrumented launches: segments, ray-sphere and ray-box tests for the
     # roofline, one per frame of the roofline's launch (passes 0 .. F-1).
     segments_local = sphere_tests = box_tests = 0
-    for k in range(F):
+    for k in range(F if args.full else 0):
         stats = torch.zeros(3, dtype=torch.int64, device="cuda")
         p = _lib.Params.from_buffer_copy(params)
         p.pass_ = k
@@ -411,14 +441,21 @@ def main() -> int:
     set_phase("timed frames")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    frames(args.warmup, args.steps)
+    last_slot, last_n = frames(args.warmup, args.steps)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
 
-    # Untimed: one launch at a time, HIP events on the launch stream.
+    if args.dump_outputs and rank == 0:
+        # The last timed step's frame as its caller holds it: the last frame of the last launch's
+        # output buffer (N > 1: of the frames that launch's gather assembled on rank 0).
+        set_phase("dump outputs")
+        src = outs[last_slot] if world == 1 else gathers[(last_slot, last_n)].full[:, :H]
+        dump_outputs(args.dump_outputs, src[last_n - 1])
+
+    # --full, untimed: one launch at a time, HIP events on the launch stream.
     def launch_ms(n, reps=3):
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
         for a, b in ev:
@@ -428,14 +465,17 @@ def main() -> int:
         torch.cuda.synchronize()
         return float(np.mean([a.elapsed_time(b) for a, b in ev]))
 
-    set_phase("launch timings")
-    kernel_ms = launch_ms(F)  # the timed launch shape: F frames, megakernel + F resolves
-    single_ms = kernel_ms if F == 1 else None if args.no_single else launch_ms(1)  # one frame, nothing overlapped
+    kernel_ms = single_ms = None
+    if args.full:
+        set_phase("launch timings")
+        kernel_ms = launch_ms(F)  # the timed launch shape: F frames, megakernel + F resolves
+        single_ms = kernel_ms if F == 1 else None if args.no_single else launch_ms(1)  # one frame, nothing overlapped
     ranks_rec = parity_n = None
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dist and args.full:
         set_phase("per-rank gather timing")
         # Untimed, per rank: the render of its rows (kernel_ms above) and one gather of F frames
         # (HIP events on the gather's stream), so a measured curve separates imbalance from the gather.
@@ -499,7 +539,7 @@ def main() -> int:
             "frames_in_flight": nslot,
             "frames_per_launch": F,
         },
-        "single_launch_ms": round(single_ms, 4) if single_ms else None,
+        "full": bool(args.full),
         "accumulation": ("fixed-point chunk sums in LDS (exact, order-free; DESIGN.md 5)" if plan["acc_slots"] > 0
                          else "fixed-point sums through the per-sample buffer" if plan["fixed_point_shift"] > 0
                          else "FP64 sum in sample order"),
@@ -508,10 +548,14 @@ def main() -> int:
     if dist_rec:
         rec["rccl_world"] = dist_rec["world"] if backend == "nccl" else None
         rec["dist"] = dist_rec
-        rec["ranks"] = ranks_rec
+        if args.full:
+            rec["ranks"] = ranks_rec
     if world > 1 and backend != "nccl":
         rec["rehearsal_backend"] = backend  # code-path check only, not a measurement
-    if rank == 0:
+    if args.dump_outputs:
+        rec["outputs"] = os.path.join(args.dump_outputs, "frame.npy")
+    if rank == 0 and args.full:
+        rec["single_launch_ms"] = round(single_ms, 4) if single_ms else None
         local_samples = rows * W * spp * F  # per launch: F frames
         ops64 = 17.0 * sphere_tests + 60.0 * segments_local + 40.0 * local_samples
         ops32 = 11.0 * box_tests
@@ -613,6 +657,35 @@ def main() -> int:
     if dist:
         dist.destroy_process_group()
     return 0
+
+
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs writes at most this much
+DUMP_SAMPLE_SEED = 20240  # the row sample of a frame larger than that: the same rows in every run
+
+
+def dump_rows(n_rows: int, row_bytes: int, limit: int = DUMP_MAX_BYTES):
+    """The rows of a frame --dump-outputs writes: all of them when the frame fits
+    `limit` bytes, else as many as fit, drawn without replacement by a generator
+    of fixed seed and sorted (the same rows for the same frame shape, always)."""
+    fit = max(1, (limit - 4096) // row_bytes)  # 4 KiB: more than the .npy header
+    if n_rows <= fit:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_rows, size=fit, replace=False))
+
+
+def dump_outputs(directory: str, frame) -> str:
+    """Write `frame` (a device or host tensor [rows, W, 3] float32, what the last
+    timed step rendered) as directory/frame.npy, float32, at most DUMP_MAX_BYTES."""
+    import torch
+
+    rows = dump_rows(frame.shape[0], int(frame[0].numel()) * 4)
+    if len(rows) < frame.shape[0]:
+        frame = frame[torch.as_tensor(rows, dtype=torch.long, device=frame.device)]
+    host = np.ascontiguousarray(frame.cpu().numpy(), dtype=np.float32)
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, "frame.npy")
+    np.save(path, host)
+    return path
 
 
 def e2e_timings(_lib, spheres, bg, cam, W, H, depth, spp, seed):

@@ -194,3 +194,40 @@ def test_rank_watchdog_is_per_phase():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and r.stdout.strip() == "done", r.stderr
     assert time.monotonic() - t0 > 3.0  # longer in total than the limit
+
+
+def test_help_lists_full_and_dump_outputs():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
+def test_dump_rows_whole_frame_or_fixed_sample():
+    """--dump-outputs writes a frame whole while it fits 64 MB (C1, C2, C5) and a
+    fixed, sorted sample of its rows above that (C3, C4): the same rows every time."""
+    import numpy as np
+
+    for name, (_, _, _, W, H, _, _) in bench.CONFIGS.items():
+        rows = bench.dump_rows(H, W * 3 * 4)
+        assert len(rows) * W * 3 * 4 + 128 <= 64 * 10**6
+        assert np.array_equal(rows, bench.dump_rows(H, W * 3 * 4))  # no state, no clock
+        assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < H
+        if W * H * 3 * 4 <= 64 * 10**6 - 4096:
+            assert np.array_equal(rows, np.arange(H)), name
+        else:
+            assert len(rows) == (64 * 10**6 - 4096) // (W * 3 * 4), name
+    assert len(bench.dump_rows(2160, 3840 * 12)) < 2160  # C3 is sampled
+    assert len(bench.dump_rows(720, 1280 * 12)) == 720  # the headline frame is whole
+
+
+def test_dump_outputs_writes_float32_frame(tmp_path):
+    import numpy as np
+    import torch
+
+    frame = torch.arange(5 * 7 * 3, dtype=torch.float32).reshape(5, 7, 3) / 3
+    path = bench.dump_outputs(str(tmp_path / "new" / "dir"), frame)
+    got = np.load(path, allow_pickle=False)
+    assert os.path.basename(path) == "frame.npy" and got.dtype == np.float32
+    assert np.array_equal(got, frame.numpy())
+    assert os.listdir(os.path.dirname(path)) == ["frame.npy"]

@@ -107,3 +107,53 @@ def test_bench_launch_shape_vs_oracle(L, O, config):
                 assert (got[ys, xs] == ref.astype(np.float32)).mean() >= 0.999
     finally:
         scene.release()
+
+
+def test_plain_bench_run_dumps_its_last_frame(L, tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run: no --full) at C1: the line holds
+    the headline fields and none of the --full legs, and DIR/frame.npy is the
+    frame of the last timed step, progressive pass warmup + steps - 1, bit for
+    bit what a single tray_render_async of that pass writes as RGB_F32."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import torch
+
+    from bench import CONFIGS
+    from conftest import ROOT
+    from tray_amd import ray
+
+    steps, warmup = 3, 1
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c1", "--steps",
+                        str(steps), "--warmup", str(warmup), "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    assert rec["steps"] == steps and rec["warmup"] == warmup and rec["full"] is False
+    assert rec["unit"] == "Mrays/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    _, seed, half, W, H, spp, depth = CONFIGS["c1"]
+    # value and ms_per_step state the same time: equal up to ms_per_step's rounding to 1e-4 ms
+    ms = rec["ms_per_step"]
+    assert abs(rec["value"] - W * H * spp / ms / 1e3) <= rec["value"] * (5e-5 / ms + 1e-6)
+    for leg in ("roofline", "e2e", "cpu_baseline", "parity", "single_launch_ms", "secondary"):
+        assert leg not in rec, leg
+    assert os.listdir(out) == ["frame.npy"]
+    got = np.load(out / "frame.npy", allow_pickle=False)
+    assert got.dtype == np.float32 and got.shape == (H, W, 3) and np.isfinite(got).all()
+
+    spheres = ray.rich_scene_array(seed, half)
+    cam = ray.RichSceneCamera()
+    cam.Initialize(W, H)
+    params = L.make_params(W, H, depth, spp, 0.5, seed, output=L.OUT_RGB_F32)
+    params.pass_ = warmup + steps - 1
+    scene = L.DeviceScene(spheres, ray._background(ray.DefaultBackground()), 0)
+    try:
+        single = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+        scene.render_async(cam._state, params, single.data_ptr(), None, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert np.array_equal(got, single.cpu().numpy())
+    finally:
+        scene.release()

@@ -40,7 +40,7 @@ def last_json(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mix", required=True)
-    ap.add_argument("--bench", required=True, help="a bench.py log (its last JSON line) of the same build")
+    ap.add_argument("--bench", required=True, help="a `bench.py --full` log (its last JSON line: the roofline record) of the same build")
     ap.add_argument("--phase", default=None)
     a = ap.parse_args()
     mix = json.load(open(a.mix))

@@ -16,15 +16,15 @@ if [ "$PART" = 1 ]; then
   # A failing GPU suite ends the evidence run: no bench or profile may come from a red tree.
   timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 180 --timeout-method thread > $O/pytest.log 2>&1
   rc=$?; if [ $rc -ne 0 ]; then echo "pytest rc=$rc" > $O/FAILED; exit $rc; fi
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $O/bench_c2.log 2>&1 || exit 1
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_c2.log 2>&1 || exit 1
   O=$O/prof bash tools/profile_configs.sh c2 || exit 1
   for n in 2 4; do
-    TRAY_BENCH_BACKEND=gloo timeout -k 10 300 python3 bench.py --gpus $n --steps 20 --warmup 5 > $O/bench_gloo$n.log 2>&1 || exit 1
+    TRAY_BENCH_BACKEND=gloo timeout -k 10 300 python3 bench.py --full --gpus $n --steps 20 --warmup 5 > $O/bench_gloo$n.log 2>&1 || exit 1
   done
   timeout -k 10 300 python3 tools/shard_sim.py --ns 1,2,4,8 --passes 16 --frames-in-flight 2 --reps 24 > $O/shard_c2.jsonl 2>&1 || exit 1
 else
   for c in $CFGS; do
-    timeout -k 10 400 python3 bench.py --config $c --steps 20 --warmup 5 > $O/bench_$c.log 2>&1 || exit 1
+    timeout -k 10 400 python3 bench.py --full --config $c --steps 20 --warmup 5 > $O/bench_$c.log 2>&1 || exit 1
   done
   O=$O/prof bash tools/profile_configs.sh $CFGS || exit 1
 fi

@@ -4,7 +4,7 @@
 set -u
 O=gpurun_out/lat; mkdir -p $O
 export TMPDIR=/tmp
-ARGS="--steps 16 --warmup 0 --no-cpu-baseline --no-e2e --no-single --frames-in-flight 1"
+ARGS="--full --steps 16 --warmup 0 --no-cpu-baseline --no-e2e --no-single --frames-in-flight 1"
 i=0
 for SET in "LdsLatency InstrFetchLatency" "VmemLatency SmemLatency" \
            "SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_LDS_IDX_ACTIVE SQ_INST_CYCLES_SALU SQ_INSTS_LDS_LOAD SQ_INSTS_LDS_STORE SQ_INSTS_LDS_ATOMIC SQ_INSTS_VSKIPPED"; do
