@@ -186,11 +186,13 @@ def phase_of(line: int, marks) -> str:
 
 # Which phase-profile counter counts the executions of each phase (per frame).
 WEIGHT = {"refill_assign": "loop_iters", "refill_cam": "refill_phases", "refill_cand": "refill_phases",
-          "refill_shade": "refill_phases", "refill_end": "loop_iters", "node_ctl": "node_iters", "node": "node_iters",
+          "refill_shade": "refill_phases", "begin": "begin_steps", "refill_end": "loop_iters",
+          "begin_end": "loop_iters", "node_ctl": "node_iters", "node": "node_iters",
           "leaf_decide": "loop_iters", "leaf_ctl": "leaf_phases", "leaf": "leaf_phases",
           "shade_ctl": "shade_phases", "shade": "shade_phases", "shade_end": "shade_phases"}
 GROUP = {"refill_assign": "refill", "refill_cam": "refill", "refill_cand": "refill", "refill_shade": "refill",
-         "refill_end": "loop", "node_ctl": "node", "node": "node", "leaf_decide": "loop", "leaf_ctl": "leaf",
+         "begin": "refill", "refill_end": "loop", "begin_end": "loop", "node_ctl": "node", "node": "node",
+         "leaf_decide": "loop", "leaf_ctl": "leaf",
          "leaf": "leaf", "shade_ctl": "shade", "shade": "shade", "shade_end": "shade"}
 
 

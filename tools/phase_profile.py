@@ -21,6 +21,8 @@ def main():
     ap.add_argument("--config", default="c2")
     ap.add_argument("--shard", default=None, help="N,K: rank K's row tiles of an N-way split (1-row tiles)")
     ap.add_argument("--refill-split", action="store_true", help="the library is a -DTRAY_PROFILE_REFILL build")
+    ap.add_argument("--begin", action="store_true",
+                    help="the library is a -DTRAY_PROFILE_BEGIN build: report the begin-step census")
     ap.add_argument("--waves", type=int, default=256 * 16, help="waves in the launch (CUs x waves per CU)")
     ap.add_argument("--material", action="store_true",
                     help="the library is a -DTRAY_PROFILE_MATERIAL build: report the shading divergence census")
@@ -53,11 +55,28 @@ def main():
     se = allv[32:32 + 2 * args.waves]
     names = ["segments", "sphere_tests", "box_tests", "cyc_refill", "cyc_node", "cyc_leaf", "cyc_shade",
              "node_iters", "node_lanes", "leaf_phases", "leaf_lanes", "shade_phases", "shade_lanes", "loop_iters", "node_leafwait_lanes", "node_shadewait_lanes", "refill_phases", "refill_lanes",
-             "unused_15", "rt_end_max", "rt_life_sum",
+             "begin_steps", "rt_end_max", "rt_life_sum",
              "rt_start_min_inv"]
     d = dict(zip(names, v))
     if args.refill_split:
         d["refill_split_share"] = {k: round(x / max(1, d["cyc_refill"]), 3) for k, x in refill_split.items()}
+    if args.begin:  # slots 10-12 hold the begin-step census: (passes << 40) + lanes
+        lo = (1 << 40) - 1
+        sh, rf, bg = d.pop("loop_iters"), d.pop("node_leafwait_lanes"), d.pop("node_shadewait_lanes")
+        d["begin"] = {
+            "readied_by_shade": {"passes": sh >> 40, "lanes": sh & lo},
+            "readied_by_refill_shade": {"passes": rf >> 40, "lanes": rf & lo},
+            "begin_steps": d["begin_steps"], "begin_lanes": bg & lo,
+            "refills_after_a_scattering_shade_pass": bg >> 40,
+        }
+        b = d["begin"]
+        b["lanes_per_begin_step"] = round(b["begin_lanes"] / max(1, b["begin_steps"]), 1)
+        b["lanes_per_shade_site_pass"] = round((sh & lo) / max(1, sh >> 40), 1)
+        b["lanes_per_refill_site_pass"] = round((rf & lo) / max(1, rf >> 40), 1)
+        b["begin_calls_saved"] = (sh >> 40) + (rf >> 40) - b["begin_steps"]
+        b["refills_adjacent_share"] = round((bg >> 40) / max(1, d["refill_phases"]), 3)
+        for k in ("loop_iters", "node_leafwait_lanes", "node_shadewait_lanes"):
+            d[k] = 0
     cyc = sum(d[k] for k in PHASES)
     d["share"] = {k: round(d[k] / cyc, 3) for k in PHASES}
     d["lanes_per_node_iter"] = round(d["node_lanes"] / max(1, d["node_iters"]), 1)
@@ -91,7 +110,7 @@ def main():
         cls = ["miss", "last", "lambertian", "metal0", "metal_fuzz", "dielectric"]
         mat = allv[32 + 2 * args.waves:]
         for site, name in enumerate(["refill_shade", "shade"]):
-            c = mat[18 * site: 18 * site + 18]
+            c = mat[26 * site: 26 * site + 26]
             passes = max(1, c[16])
             d["material_" + name] = {
                 "passes": c[16], "lanes": c[17], "lanes_per_pass": round(c[17] / passes, 2),
@@ -99,6 +118,8 @@ def main():
                 "lanes_of": {k: c[6 + i] for i, k in enumerate(cls)},
                 "lanes_per_pass_with": {k: round(c[6 + i] / max(1, c[i]), 2) for i, k in enumerate(cls)},
                 "bodies_per_pass": {str(b): round(c[12 + b] / passes, 4) for b in range(4)},
+                "passes_by_dielectric_lanes": dict(zip(["1", "2-3", "4-7", ">=8"], c[18:22])),
+                "passes_by_metal_lanes": dict(zip(["1", "2-3", "4-7", ">=8"], c[22:26])),
             }
     print(json.dumps(d))
 

@@ -412,7 +412,9 @@ __device__ __forceinline__ float f32_up(double v) {
 // Lane states of the BVH kernel, encoded in Trav::cur (no state register, no
 // per-step state bookkeeping): an inner node (< kBvhLeafBit) = traversing; a
 // leaf reference = waiting for the leaf phase; kBvhNone = traversal done,
-// waiting for the shade phase (busy lane) or idle (Lane::busy false).
+// waiting for the shade phase (busy lane) or idle (Lane::busy false);
+// kTravReady = the ray of a new segment is in Lane::org / dir and its setup
+// (trav_begin) is still to run, in the kernel loop's begin step.
 
 struct Trav {
     float ix, iy, iz, oix, oiy, oiz;  // FP32 ray: t = box * inv - org * inv
@@ -472,6 +474,9 @@ __device__ __forceinline__ void stack_store(const Stk& S, int32_t i, uint32_t v)
 // over its 16-bit reference. ~0 = no entry.
 __device__ __forceinline__ float key_tn(uint32_t key) { return __uint_as_float(key & 0xFFFF0000u); }
 
+// Above every child reference and kBvhNone: neither is_trav nor is_leaf, not waiting
+// for the shade phase (cur == kBvhNone) and not work in flight (cur < kBvhNone).
+constexpr uint32_t kTravReady = kBvhNone + 1u;
 __device__ __forceinline__ bool is_trav(uint32_t cur) { return cur < kBvhLeafBit; }
 __device__ __forceinline__ bool is_leaf(uint32_t cur) { return cur - kBvhLeafBit < kBvhNone - kBvhLeafBit; }
 
@@ -1175,6 +1180,11 @@ constexpr int32_t kDeepNodes = 384;
 // phase of the BVH loop, plus phase and active-lane counts, added into
 // stats[3..21] (the stats buffer must then hold 22 counters). Never part of a
 // timed build: the stamps' waits serialise the phases.
+// With -DTRAY_PROFILE_BEGIN the census of the begin step replaces slots 10-12
+// (tools/phase_profile.py --begin): [10] / [11] segments readied by the shade phase /
+// by the refill's camera-hit shading, as (passes << 40) + lanes; [12] (refills that
+// found segments readied by the shade phase just before << 40) + lanes of the begin
+// steps. Slot 15 counts the begin steps in every profile build.
 #ifdef TRAY_PROFILE
 // Counters live in LDS (per wave, lane 0 adds): registers would change the
 // kernel being measured.
@@ -1203,10 +1213,14 @@ constexpr int32_t kDeepNodes = 384;
 // refill, 1: the shade phase) and per class of shaded lane (0 miss/sky, 1 hit at
 // the last level, 2 Lambertian, 3 Metal without fuzz, 4 Metal with fuzz, 5
 // Dielectric): [c] passes with such a lane, [6 + c] such lanes; [12 + b] passes
-// executing b of the three material bodies (b = 0..3); [16] passes, [17] lanes.
+// executing b of the three material bodies (b = 0..3); [16] passes, [17] lanes;
+// [18 + h] / [22 + h] passes with 1, 2-3, 4-7, >= 8 Dielectric / Metal lanes.
 // Added with global atomics after the per-wave stamps (stats[32 + 2 x waves + k]).
+#if defined(TRAY_PROFILE_BEGIN) && (defined(TRAY_PROFILE_REFILL) || defined(TRAY_PROFILE_CANDWAIT))
+#error "TRAY_PROFILE_BEGIN shares profile slots with TRAY_PROFILE_REFILL / TRAY_PROFILE_CANDWAIT"
+#endif
 #ifdef TRAY_PROFILE_MATERIAL
-constexpr int kMatCounters = 18;
+constexpr int kMatCounters = 26;
 __device__ __forceinline__ void prof_material(int site, bool active, int32_t slot, uint32_t bounce, int32_t max_depth,
                                               const MatRec* bmat, uint32_t lane, unsigned long long* pm) {
     int cls = -1;
@@ -1228,7 +1242,10 @@ __device__ __forceinline__ void prof_material(int site, bool active, int32_t slo
         }
     }
     bodies = (__ballot(cls == 2) ? 1 : 0) + (__ballot(cls == 3 || cls == 4) ? 1 : 0) + (__ballot(cls == 5) ? 1 : 0);
+    const int n_di = __popcll(__ballot(cls == 5)), n_me = __popcll(__ballot(cls == 3 || cls == 4));
     if (lane == 0) {
+        if (n_di) atomicAdd(c + 18 + (n_di >= 8 ? 3 : n_di >= 4 ? 2 : n_di >= 2 ? 1 : 0), 1ull);
+        if (n_me) atomicAdd(c + 22 + (n_me >= 8 ? 3 : n_me >= 4 ? 2 : n_me >= 2 ? 1 : 0), 1ull);
         atomicAdd(c + 12 + bodies, 1ull);
         atomicAdd(c + 16, 1ull);
         atomicAdd(c + 17, (unsigned long long)__popcll(__ballot(active)));
@@ -1428,8 +1445,8 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             }
         }
 #endif
-#ifndef TRAY_PROFILE_REFILL  // slots 10, 13-15 hold the refill split instead
-        PROF_CNT(10, 1);
+#if !defined(TRAY_PROFILE_REFILL) && !defined(TRAY_PROFILE_BEGIN)  // slots 10, 13-15 hold the refill split
+        PROF_CNT(10, 1);                                               // instead, or 10-12 the begin-step census
 #endif
         // Refill idle lanes from the wave's pool, fetching 64-item chunks from the global queue.
         PROF_T0();
@@ -1523,6 +1540,9 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             const uint64_t fresh = __ballot(fresh_item != ~0u);
             PROF_CNT(13, fresh != 0ull ? 1 : 0);
             PROF_CNT(14, __popcll(fresh));
+#ifdef TRAY_PROFILE_BEGIN  // refills that find segments readied by the shade phase just before
+            if constexpr (kBVH) PROF_CNT(12, (uint64_t)(fresh != 0ull && __ballot(T.cur == kTravReady) != 0ull) << 40);
+#endif
         }
 #endif
 #ifdef TRAY_PROFILE_REFILL
@@ -1601,13 +1621,18 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                     if (shade_step<kStats, kAcc>(kp_fresh(), L, T.slot, T.closest, T.a, [&] { return sv.bgeo[max(T.slot, 0)]; },
                                                  [&] { return sv.bmat[max(T.slot, 0)]; }, st, acc)) {
                         ++L.segments;
-                        trav_begin(T, sv, L.org, L.dir);
-                        if constexpr (kStats) st.spheres += (uint64_t)sv.n_global;
+                        T.cur = kTravReady;  // set up by the begin step below
                     } else {
                         ended = true;
                     }
                 }
                 if constexpr (kProg) count_progress(p, ended, L.j, lane, prog_cur, prog_cnt);
+#ifdef TRAY_PROFILE_BEGIN
+                {
+                    const uint64_t m = __ballot(cam_hit && T.cur == kTravReady);
+                    PROF_CNT(11, ((uint64_t)(m != 0ull) << 40) + (uint64_t)__popcll(m));
+                }
+#endif
             }
         }
 #ifdef TRAY_PROFILE_REFILL
@@ -1659,6 +1684,34 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             }
             if constexpr (kProg) count_progress(p, ended, L.j, lane, prog_cur, prog_cnt);
         } else {
+            // Begin step: the setup of every new segment (trav_begin: |dir|^2 and its
+            // reciprocal, the out-of-tree spheres' Sphere.Hit, the FP32 traversal setup),
+            // once per iteration, for the rays scattered by the last shade phase and by the
+            // refill's camera-hit shading above together. The two used to set up their own
+            // lanes back to back (a shade phase frees the lanes that trigger the next
+            // refill), each on a minority of the wave; the same instructions now run once,
+            // on both sets.
+            // Invariant: a lane is kTravReady only from the end of the shade phase or of the
+            // refill's shading to this step, and this step leaves no lane in that state.
+            // Between them lie only loop control, the refill (which handles idle lanes) and
+            // the exit test above, which a ready lane fails (it is busy): the loop's exit,
+            // the drain, the node steps, the leaf phase and the shade phase never see the state.
+            {
+                PROF_T0();
+#if defined(TRAY_PROFILE) && !defined(TRAY_PROFILE_REFILL) && !defined(TRAY_PROFILE_CANDWAIT)  // (they time into slot 15)
+                PROF_CNT(15, __ballot(T.cur == kTravReady) != 0ull ? 1 : 0);
+#endif
+#ifdef TRAY_PROFILE_BEGIN
+                PROF_CNT(12, __popcll(__ballot(T.cur == kTravReady)));
+#endif
+                if (T.cur == kTravReady) {
+                    TRAY_MARK("begin")
+                    trav_begin(T, sv, L.org, L.dir);
+                    if constexpr (kStats) st.spheres += (uint64_t)sv.n_global;
+                }
+                PROF_ADD(0);  // counted with the refill
+                TRAY_MARK("begin_end")
+            }
             if constexpr (kLDS == 1) {
                 // The drain: a dry wave with at most coop_lanes paths finds their hits
                 // with the whole wave (coop_hit; the node steps below then find none).
@@ -1689,8 +1742,10 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                     if (s >= TRAY_NODE_STEPS && __popcll(m) < TRAY_NODE_MORE_LANES) break;
                     PROF_CNT(4, 1);
                     PROF_CNT(5, __popcll(m));
+#ifndef TRAY_PROFILE_BEGIN
                     PROF_CNT(11, __popcll(__ballot(is_leaf(T.cur))));             // waiting for the leaf phase
                     PROF_CNT(12, __popcll(__ballot(L.busy && T.cur == kBvhNone)));  // waiting for the shade phase
+#endif
                     if (is_trav(T.cur)) {
                         TRAY_MARK("node")
                         uint32_t tested;
@@ -1785,13 +1840,18 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                             }
                         }
 #endif
-                        trav_begin(T, sv, L.org, L.dir);
-                        if constexpr (kStats) st.spheres += (uint64_t)sv.n_global;
+                        T.cur = kTravReady;  // set up by the begin step of the next iteration
                     } else {
                         ended = true;  // idle: T.cur stays kBvhNone, L.busy is false
                     }
                 }
                 if constexpr (kProg) count_progress(p, ended, L.j, lane, prog_cur, prog_cnt);
+#ifdef TRAY_PROFILE_BEGIN
+                {
+                    const uint64_t m = __ballot(T.cur == kTravReady);
+                    PROF_CNT(10, ((uint64_t)(m != 0ull) << 40) + (uint64_t)__popcll(m));
+                }
+#endif
                 PROF_ADD(3);
                 TRAY_MARK("shade_end")
             }
