@@ -157,6 +157,34 @@ EXPORTS = (
     "tray_linear_to_srgba_async",
 )
 
+# Every symbol include/tray_query.h declares (batched ray queries; not in EXPORTS).
+QUERY_EXPORTS = (
+    "tray_query_version",
+    "tray_camera_rays_async",
+    "tray_scene_hit_async",
+    "tray_ray_color_async",
+)
+
+# tray_ray / tray_hit (include/tray_query.h) as numpy structured dtypes, C layout.
+RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("direction", "<f8", (3,))])
+HIT_DTYPE = np.dtype([("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("t", "<f8"), ("index", "<i4"),
+                      ("front_face", "<i4")])
+assert RAY_DTYPE.itemsize == 48 and HIT_DTYPE.itemsize == 64
+
+
+class Ray(ctypes.Structure):
+    """tray_ray."""
+    _fields_ = [("origin", _d3), ("direction", _d3)]
+
+
+class Hit(ctypes.Structure):
+    """tray_hit."""
+    _fields_ = [("point", _d3), ("normal", _d3), ("t", ctypes.c_double), ("index", ctypes.c_int32),
+                ("front_face", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Ray) == 48 and ctypes.sizeof(Hit) == 64
+
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
 DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear")
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
@@ -237,6 +265,11 @@ def lib(path: str | None = None) -> ctypes.CDLL:
     L.tray_params_rows.argtypes = [ctypes.POINTER(Params)]
     L.tray_params_rows.restype = i32
     L.tray_to_srgba.argtypes = [vp, ctypes.c_size_t, vp]
+    if hasattr(L, "tray_query_version"):  # include/tray_query.h; absent from older builds (A/B tools)
+        L.tray_query_version.restype = i32
+        L.tray_camera_rays_async.argtypes = [ctypes.POINTER(CameraState), ctypes.POINTER(Params), i32, vp, vp, vp]
+        L.tray_scene_hit_async.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_double, i32, vp, vp]
+        L.tray_ray_color_async.argtypes = [vp, vp, vp, ctypes.c_int64, i32, ctypes.c_uint64, i32, vp, vp, vp]
     if hasattr(L, "tray_debug_set"):  # absent from older builds (A/B tools)
         L.tray_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
         L.tray_debug_clear.argtypes = [ctypes.c_char_p]
@@ -445,6 +478,18 @@ def linear_to_srgba_async(rgb_ptr: int, n_pixels: int, rgba_ptr: int, device: in
     check(lib().tray_linear_to_srgba_async(rgb_ptr, n_pixels, rgba_ptr, device, stream))
 
 
+def camera_rays_count(params: Params) -> int:
+    """Rays tray_camera_rays_async writes for `params`: rows x width x rays_per_pixel."""
+    return params_rows(params) * params.width * params.rays_per_pixel
+
+
+def camera_rays_async(camera: CameraState, params: Params, rays_ptr: int, ids_ptr: int | None = None,
+                      device: int = 0, stream: int | None = None) -> None:
+    """tray_camera_rays_async: Camera.GetRay for every sample of params' row set into
+    device buffers (camera_rays_count(params) x tray_ray; ids: 2 x uint32 per ray)."""
+    check(lib().tray_camera_rays_async(ctypes.byref(camera), ctypes.byref(params), device, rays_ptr, ids_ptr, stream))
+
+
 class DeviceScene:
     """A scene uploaded once to one device (tray_scene_upload); render many times,
     from any thread and on any streams: each render runs in a launch context of
@@ -483,6 +528,23 @@ class DeviceScene:
         """Instrumented render (f32 output); stats_ptr -> 3 x uint64: segments, sphere tests, box tests."""
         rc = self.L.tray_render_stats_async(self.handle, ctypes.byref(camera), ctypes.byref(params), out_ptr,
                                             stats_ptr, stream)
+        if rc != TRAY_OK:
+            raise TrayError(rc, self.L.tray_last_error().decode())
+
+    def hit_async(self, rays_ptr: int, n: int, hits_ptr: int, t_end: float = float("inf"), flags: int = 0,
+                  stream: int | None = None) -> None:
+        """tray_scene_hit_async: Scene.Hit(r, Interval{1e-6, t_end}) for n device rays -> n x tray_hit."""
+        rc = self.L.tray_scene_hit_async(self.handle, rays_ptr, int(n), float(t_end), int(flags), hits_ptr, stream)
+        if rc != TRAY_OK:
+            raise TrayError(rc, self.L.tray_last_error().decode())
+
+    def ray_color_async(self, rays_ptr: int, n: int, max_depth: int, seed: int, rgb_ptr: int,
+                        ids_ptr: int | None = None, segments_ptr: int | None = None, flags: int = 0,
+                        stream: int | None = None) -> None:
+        """tray_ray_color_async: Scene.RayColor(r, max_depth) for n device rays -> n x 3 f64
+        (+ n x uint32 Scene.Hit counts); ids: the (pixel, sample word) pair of each ray's draws."""
+        rc = self.L.tray_ray_color_async(self.handle, rays_ptr, ids_ptr, int(n), int(max_depth),
+                                         int(seed) & (2**64 - 1), int(flags), rgb_ptr, segments_ptr, stream)
         if rc != TRAY_OK:
             raise TrayError(rc, self.L.tray_last_error().decode())
 

@@ -25,6 +25,7 @@
 #include "bvh.hpp"
 #include "rng.hpp"
 #include "tray_kernel.hpp"
+#include "tray_query.hpp"
 
 namespace tray {
 
@@ -566,6 +567,44 @@ static int32_t fixed_point_shift(const tray_scene_s* sc, const tray_params* p) {
     return k >= kAccMinShift ? std::min(k, 600) : 0;
 }
 
+// The scene's arrays and background in the kernel parameters (renders and ray queries).
+static void scene_params(const tray_scene_s* sc, KernelParams& k) {
+    k.geo = sc->geo;
+    k.mat = sc->mat;
+    k.n = sc->n;
+    k.n_pad = sc->n_pad;
+    k.bg_a = sc->bg_a;
+    k.bg_b = sc->bg_b;
+    k.srgb = sc->srgb;
+    k.nodes = sc->nodes;
+    k.bgeo = sc->bgeo;
+    k.bidx = sc->bidx;
+    k.bmat = sc->bmat;
+    k.n_nodes = sc->n_nodes;
+    k.n_slots = sc->n_slots;
+    k.n_leaves = sc->n_leaves;
+    k.n_global = sc->n_global;
+    k.leaves = sc->leaves;
+    k.leaf_single = sc->leaf_max == 1 ? 1 : 0;
+    k.stack_cap = sc->stack_cap;
+}
+
+// The camera and the draw key of `seed` in the kernel parameters (get_ray, draw).
+static void camera_params(const tray_camera* cam, KernelParams& k) {
+    k.focus_time = cam->focus_distance / cam->focal_length;  // ray/camera.go:134
+    memcpy(k.cam.position, cam->position, sizeof(k.cam.position));
+    memcpy(k.cam.pixel00, cam->pixel00, sizeof(k.cam.pixel00));
+    memcpy(k.cam.pixel_x, cam->pixel_x, sizeof(k.cam.pixel_x));
+    memcpy(k.cam.pixel_y, cam->pixel_y, sizeof(k.cam.pixel_y));
+    memcpy(k.cam.defocus_u, cam->defocus_u, sizeof(k.cam.defocus_u));
+    memcpy(k.cam.defocus_v, cam->defocus_v, sizeof(k.cam.defocus_v));
+    k.cam.aperture = cam->aperture;
+}
+static void key_params(uint64_t seed, KernelParams& k) {
+    const DrawKey dk = draw_key(seed);  // include/tray.h, ABI 6
+    k.key[0] = dk.k0, k.key[1] = dk.k1, k.key[2] = dk.k2, k.key[3] = dk.k3;
+}
+
 // The kernel parameters of a render of `p` on `sc` (everything but the output,
 // instrumentation and workspace pointers) and whether it runs the BVH kernel.
 static int prepare_render(tray_scene_t sc, const tray_camera* cam, const tray_params* p, int32_t n_passes,
@@ -580,10 +619,7 @@ static int prepare_render(tray_scene_t sc, const tray_camera* cam, const tray_pa
     if (!band_fits(p->width, spp_launch))
         return fail(TRAY_ERR_TOO_LARGE, "width x rays_per_pixel x passes too large (8 rows of samples exceed 2^31)");
     memset(&k, 0, sizeof(k));
-    k.geo = sc->geo;
-    k.mat = sc->mat;
-    k.n = sc->n;
-    k.n_pad = sc->n_pad;
+    scene_params(sc, k);
     k.width = p->width;
     k.height = p->height;
     k.spp = p->rays_per_pixel;
@@ -595,20 +631,8 @@ static int prepare_render(tray_scene_t sc, const tray_camera* cam, const tray_pa
     k.tile_index = p->tile_rows > 0 ? p->tile_index : 0;
     k.out_format = p->output;
     k.ray_radius = p->ray_radius;
-    k.focus_time = cam->focus_distance / cam->focal_length;  // ray/camera.go:134
-    {
-        const DrawKey dk = draw_key(p->seed);  // include/tray.h, ABI 6
-        k.key[0] = dk.k0, k.key[1] = dk.k1, k.key[2] = dk.k2, k.key[3] = dk.k3;
-    }
-    memcpy(k.cam.position, cam->position, sizeof(k.cam.position));
-    memcpy(k.cam.pixel00, cam->pixel00, sizeof(k.cam.pixel00));
-    memcpy(k.cam.pixel_x, cam->pixel_x, sizeof(k.cam.pixel_x));
-    memcpy(k.cam.pixel_y, cam->pixel_y, sizeof(k.cam.pixel_y));
-    memcpy(k.cam.defocus_u, cam->defocus_u, sizeof(k.cam.defocus_u));
-    memcpy(k.cam.defocus_v, cam->defocus_v, sizeof(k.cam.defocus_v));
-    k.cam.aperture = cam->aperture;
-    k.bg_a = sc->bg_a;
-    k.bg_b = sc->bg_b;
+    camera_params(cam, k);
+    key_params(p->seed, k);
     k.acc_shift = fixed_point_shift(sc, p);
     if (k.acc_shift > 0) {  // the scale rides on the background: every colour is then scaled (exactly)
         for (V3* v : {&k.bg_a, &k.bg_b}) {
@@ -620,18 +644,6 @@ static int prepare_render(tray_scene_t sc, const tray_camera* cam, const tray_pa
     k.passes = (uint32_t)n_passes;
     k.pass0 = (uint32_t)p->pass;
     k.out_frame_bytes = (size_t)k.rows * (size_t)p->width * bytes_per_pixel(p->output);
-    k.srgb = sc->srgb;
-    k.nodes = sc->nodes;
-    k.bgeo = sc->bgeo;
-    k.bidx = sc->bidx;
-    k.bmat = sc->bmat;
-    k.n_nodes = sc->n_nodes;
-    k.n_slots = sc->n_slots;
-    k.n_leaves = sc->n_leaves;
-    k.n_global = sc->n_global;
-    k.leaves = sc->leaves;
-    k.leaf_single = sc->leaf_max == 1 ? 1 : 0;
-    k.stack_cap = sc->stack_cap;
     {
         long long coop = TRAY_COOP_LANES;
         (void)debug_knob(kKnobCoopLanes, &coop);  // A/B and tests: the drain's wave-wide Scene.Hit
@@ -859,6 +871,90 @@ int tray_render_stats_async(tray_scene_t sc, const tray_camera* cam, const tray_
 }
 
 // Grows a device workspace to `bytes` (contents not kept).
+// ---- ray queries (include/tray_query.h) ----------------------------------------
+int32_t tray_query_version(void) { return TRAY_QUERY_VERSION; }
+
+constexpr int64_t kQueryMaxRays = 0x7FFFFFFF;  // ray indices are 32-bit on the device
+
+// The checks the scene queries share, before any device work.
+static int validate_query(tray_scene_t sc, const void* rays, int64_t n, int32_t flags, const void* out) {
+    if (n < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative ray count");
+    if (n > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 rays in one query");
+    if (flags & ~TRAY_FLAG_LINEAR_SCAN)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "unknown flags (a query takes TRAY_FLAG_LINEAR_SCAN only)");
+    if (n > 0 && !rays) return fail(TRAY_ERR_INVALID_ARGUMENT, "null ray buffer");
+    if (n > 0 && !out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null result buffer");
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    return TRAY_OK;
+}
+
+int tray_camera_rays_async(const tray_camera* cam, const tray_params* p, int32_t device, tray_ray* rays_device,
+                           uint32_t* ids_device, void* stream) {
+    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
+    int rc = validate_params(p);
+    if (rc) return rc;
+    const int64_t rows = tray_params_rows(p);
+    if (rows * (int64_t)p->width > kQueryMaxRays / p->rays_per_pixel)
+        return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 camera rays in one query");
+    const int64_t n = rows * (int64_t)p->width * (int64_t)p->rays_per_pixel;
+    if (n > 0 && !rays_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null ray buffer");
+    if (n == 0) return TRAY_OK;
+    rc = device_usable(device);
+    if (rc) return rc;
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    k.width = p->width;
+    k.height = p->height;
+    k.spp = p->rays_per_pixel;
+    k.y_start = p->y_start;
+    k.rows = (int32_t)rows;
+    k.tile_rows = p->tile_rows;
+    k.tile_count = p->tile_rows > 0 ? p->tile_count : 1;
+    k.tile_index = p->tile_rows > 0 ? p->tile_index : 0;
+    k.ray_radius = p->ray_radius;
+    k.passes = 1;
+    k.pass0 = (uint32_t)p->pass;
+    camera_params(cam, k);
+    key_params(p->seed, k);
+    TRAY_HIP(hipSetDevice(device));
+    TRAY_HIP(launch_camera_rays(k, rays_device, ids_device, (uint32_t)n, static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
+int tray_scene_hit_async(tray_scene_t sc, const tray_ray* rays_device, int64_t n, double t_end, int32_t flags,
+                         tray_hit* hits_device, void* stream) {
+    if (t_end != t_end) return fail(TRAY_ERR_INVALID_ARGUMENT, "t_end is NaN");
+    int rc = validate_query(sc, rays_device, n, flags, hits_device);
+    if (rc) return rc;
+    if (n == 0) return TRAY_OK;
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    TRAY_HIP(hipSetDevice(sc->device));
+    TRAY_HIP(launch_scene_hit(k, sc->has_bvh && !(flags & TRAY_FLAG_LINEAR_SCAN), sc->bvh_bound, rays_device,
+                              (uint32_t)n, t_end, hits_device, static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
+int tray_ray_color_async(tray_scene_t sc, const tray_ray* rays_device, const uint32_t* ids_device, int64_t n,
+                         int32_t max_depth, uint64_t seed, int32_t flags, double* rgb_device,
+                         uint32_t* segments_device, void* stream) {
+    if (max_depth <= 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "max_depth must be > 0");
+    int rc = validate_query(sc, rays_device, n, flags, rgb_device);
+    if (rc) return rc;
+    if (n == 0) return TRAY_OK;
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    key_params(seed, k);
+    k.max_depth = max_depth;
+    TRAY_HIP(hipSetDevice(sc->device));
+    TRAY_HIP(launch_ray_color(k, sc->has_bvh && !(flags & TRAY_FLAG_LINEAR_SCAN), sc->bvh_bound, rays_device,
+                              ids_device, (uint32_t)n, rgb_device, segments_device,
+                              static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
 static hipError_t grow(void** buf, size_t* have, size_t bytes) {
     if (*have >= bytes) return hipSuccess;
     if (*buf) (void)hipFree(*buf);

@@ -1098,6 +1098,13 @@ __device__ __forceinline__ bool shade_step(const KernelParams& p, Lane& L, int b
     return false;
 }
 
+// tray_query.hip includes this file for the device functions above only (its kernels
+// call the same get_ray, test_geo and trav_* as the megakernel): with
+// TRAY_DEVICE_FUNCTIONS_ONLY the megakernel, its helper kernels and the host side
+// below are left out. This translation unit never defines it, so what it compiles is
+// unchanged.
+#ifndef TRAY_DEVICE_FUNCTIONS_ONLY
+
 #ifndef TRAY_WAVES_PER_SIMD
 #define TRAY_WAVES_PER_SIMD 5
 #endif
@@ -2592,5 +2599,7 @@ hipError_t launch_render(KernelParams p, bool use_bvh, const LaunchPlan& plan, h
     }
     return hipSuccess;
 }
+
+#endif  // TRAY_DEVICE_FUNCTIONS_ONLY
 
 }  // namespace tray

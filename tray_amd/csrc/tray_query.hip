@@ -1,0 +1,320 @@
+// tray_query.hip — batched ray queries on an uploaded scene for gfx950
+// (include/tray_query.h): Camera.GetRay (ray/camera.go:113-142), Scene.Hit
+// (ray/objects.go:37-46, Sphere.Hit :81-104) and Scene.RayColor
+// (ray/objects.go:49-62) as kernels of their own, one ray (sample, path) per
+// lane.
+//
+// The arithmetic is the megakernel's, not a restatement of it: this file
+// includes tray_kernel.hip's device functions (get_ray, camera_block, draw,
+// quad, test_geo, trav_globals, trav_begin32, trav_node, trav_leaf,
+// scene_hit_linear, unit_lsq, sdiv_rcp, reflect, refract, ...) and leaves its
+// kernels and host side out. The one exception is the scatter step
+// (query_shade below), the twin of shade_step: that function is tied to the
+// megakernel's lane state and pixel sums, and factoring the arithmetic out of it
+// would have changed the product instances ("Ray queries").
+// Compiled with -ffp-contract=off like every other unit.
+
+#define TRAY_DEVICE_FUNCTIONS_ONLY
+#include "tray_kernel.hip"
+
+#include "tray_query.hpp"
+
+namespace tray {
+
+// Workgroup of the hit and colour kernels. The scene (nodes, leaf table, geometry,
+// shading records) is read through L2, not staged: a workgroup traces 256 rays and
+// ends, so a per-workgroup LDS copy of the scene is re-made every 256 rays and its
+// LDS lowers the occupancy (measured on C2, DESIGN.md "Ray queries": staging the
+// book cover's BVH made the hit query 1.45x and the colour query 1.57x slower).
+// Only the traversal stacks live in LDS.
+constexpr int kQueryBlock = 256;
+static_assert(kQueryBlock % 64 == 0, "whole waves");
+
+// The traversal stack policy of the queries (trav_node / trav_leaf take any policy
+// with these two accessors): the megakernel's layout, slot i of a lane at
+// base[i * lanes of the workgroup], for kQueryBlock lanes: stack_cap x 1 KB of LDS
+// per workgroup. No spill area: a scene whose stack does not fit takes the linear
+// scan (launch_*).
+struct QStack {
+    static constexpr bool spill = false;
+    __attribute__((address_space(3))) uint32_t* base;  // this lane's slot 0
+};
+__device__ __forceinline__ uint32_t stack_load(const QStack& S, int32_t i) { return S.base[i * kQueryBlock]; }
+__device__ __forceinline__ void stack_store(const QStack& S, int32_t i, uint32_t v) { S.base[i * kQueryBlock] = v; }
+
+struct QueryArgs {
+    const tray_ray* rays;
+    const uint32_t* ids;  // colour, nullable: (pixel, sample word) per ray
+    void* out;            // tray_hit per ray / 3 doubles per ray
+    uint32_t* segments;   // colour, nullable
+    uint32_t n;
+    int32_t use_bvh;      // 0: every ray takes the linear scan
+    double bound;         // M: the BVH needs ray origins in [-M, M]^3 (tray_bvh.cpp)
+    double t_end;         // hit: Interval.End
+};
+
+__device__ __forceinline__ SceneView scene_view(const KernelParams& p) {
+    return SceneView{p.geo,  p.nodes, p.leaves,  p.leaf_single != 0, p.bgeo,          p.bidx,
+                     p.bmat, p.n,     p.n_nodes, p.n_global,         p.n_slots - p.n_global};
+}
+
+__device__ __forceinline__ D3 ray_origin(const tray_ray* rays, uint32_t i) {
+    return d3(rays[i].origin[0], rays[i].origin[1], rays[i].origin[2]);
+}
+__device__ __forceinline__ D3 ray_direction(const tray_ray* rays, uint32_t i) {
+    return d3(rays[i].direction[0], rays[i].direction[1], rays[i].direction[2]);
+}
+
+// Scene.Hit(r, Interval{1e-6, t_end}): the hit's root and where its sphere's records
+// are (`ref`: a leaf slot when `tree`, else the list index; -1: no hit).
+struct QHit {
+    double t;
+    double a;  // |dir|^2 (same bits as Sphere.Hit's per sphere)
+    int32_t ref;
+    bool tree;
+};
+
+// Per ray: the BVH when the launch has one, the origin lies inside the bound its
+// padding proof needs, and the direction is finite and of a length FP32 can carry
+// (trav_begin32 clamps components below 1e-30); any other ray takes the
+// reference-order linear scan, which has no such conditions. Both give
+// min over spheres of (t_i, i) with t_i in (1e-6, t_end) (the any-order rule,
+// tray_kernel.hip): the traversal by starting its culling distance at t_end,
+// where a root equal to t_end loses because no hit is held yet; the scan by
+// dropping a closest hit that is not below t_end.
+__device__ __forceinline__ QHit query_hit(const SceneView& sv, const QStack& S, const QueryArgs& q, const D3& org,
+                                          const D3& dir, double t_end) {
+    QHit h;
+    h.a = length_sq(dir);
+    h.t = t_end;
+    h.ref = -1;
+    const double M = q.bound;
+    const bool inside = __builtin_fabs(org.x) <= M && __builtin_fabs(org.y) <= M && __builtin_fabs(org.z) <= M;
+    h.tree = q.use_bvh != 0 && inside && h.a >= 1e-30 && h.a <= 1e30;
+    if (!(t_end > 1e-6)) return h;  // an empty interval surrounds no root
+    if (h.tree) {
+        Trav T;
+        T.tlim = __builtin_inff();
+        trav_globals(T, sv, org, dir);
+        if (!(T.closest < t_end)) {  // nothing closer than t_end among the out-of-tree spheres
+            T.closest = t_end;
+            T.slot = -1;
+        }
+        trav_begin32(T, sv, org, dir);
+        uint32_t tested;
+        while (T.cur != kBvhNone) {
+            if (is_trav(T.cur)) trav_node(T, sv, S, tested);
+            else trav_leaf(T, sv, S, org, dir, tested);
+        }
+        h.t = T.closest;
+        h.ref = T.slot;
+    } else {
+        Stats st;
+        double closest;
+        const int best = scene_hit_linear<TRAY_UNROLL, false>(sv, org, dir, closest, st);
+        if (best >= 0 && closest < t_end) {
+            h.t = closest;
+            h.ref = best;
+        }
+    }
+    return h;
+}
+
+__device__ __forceinline__ QStack lane_stack() {
+    extern __shared__ __attribute__((aligned(16))) uint32_t query_stacks[];
+    return QStack{(__attribute__((address_space(3))) uint32_t*)query_stacks + threadIdx.x};
+}
+
+// Camera.GetRay: lane i is sample s of pixel (x, compact row j), i = (j * width + x) * r + s.
+__global__ __launch_bounds__(256) void camera_rays_kernel(KernelParams p, tray_ray* rays, uint32_t* ids, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t spp = (uint32_t)p.spp, width = (uint32_t)p.width;
+    const uint32_t s = i % spp, q = i / spp;
+    const uint32_t x = q % width, j = q / width;
+    const int32_t y = row_of(p, (int32_t)j);
+    const uint32_t pixel = (uint32_t)y * width + x;    // global index: the draw block's pixel word
+    const uint32_t sample = p.pass0 * spp + s;          // the draw block's sample word
+    D3 org, dir;
+    get_ray(p, camera_block(p, pixel, sample), (double)x, (double)y, org, dir);
+    tray_ray* r = rays + i;
+    r->origin[0] = org.x, r->origin[1] = org.y, r->origin[2] = org.z;
+    r->direction[0] = dir.x, r->direction[1] = dir.y, r->direction[2] = dir.z;
+    if (ids) {
+        ids[2 * (size_t)i] = pixel;
+        ids[2 * (size_t)i + 1] = sample;
+    }
+}
+
+// Scene.Hit: one ray per lane. The record is Sphere.Hit's (ray/objects.go:98-102):
+// Point = r.At(t), the outward normal (P - C) / R as a correctly rounded quotient
+// (sdiv_rcp with the host's RN(1 / R), as shade_step), SetFaceNormal.
+__global__ __launch_bounds__(kQueryBlock) void scene_hit_kernel(KernelParams p, QueryArgs q) {
+    const uint32_t i = blockIdx.x * kQueryBlock + threadIdx.x;
+    if (i >= q.n) return;
+    const SceneView sv = scene_view(p);
+    const QStack S = lane_stack();
+    const D3 org = ray_origin(q.rays, i), dir = ray_direction(q.rays, i);
+    const QHit h = query_hit(sv, S, q, org, dir, q.t_end);
+    tray_hit* o = static_cast<tray_hit*>(q.out) + i;
+    if (h.ref < 0) {
+        o->point[0] = o->point[1] = o->point[2] = 0.0;
+        o->normal[0] = o->normal[1] = o->normal[2] = 0.0;
+        o->t = 0.0;
+        o->index = -1;
+        o->front_face = 0;
+        return;
+    }
+    const double4 g = h.tree ? sv.bgeo[h.ref] : sv.geo[h.ref];
+    const MatRec* m = h.tree ? sv.bmat + h.ref : p.mat + h.ref;
+    const double radius = m->radius, rinv = m->rinv;
+    const D3 point = add(org, smul(dir, h.t));                                 // Ray.At (ray/ray.go:23-25)
+    const D3 outward = sdiv_rcp(sub(point, d3(g.x, g.y, g.z)), radius, rinv);  // ray/objects.go:100
+    const bool front = dot(dir, outward) < 0;                                  // SetFaceNormal (:19-26)
+    const D3 normal = neg_if(outward, !front);
+    o->point[0] = point.x, o->point[1] = point.y, o->point[2] = point.z;
+    o->normal[0] = normal.x, o->normal[1] = normal.y, o->normal[2] = normal.z;
+    o->t = h.t;
+    o->index = h.tree ? sv.bidx[h.ref] : h.ref;
+    o->front_face = front ? 1 : 0;
+}
+
+// One recursion level of RayColor after Scene.Hit gave `h`: THE TWIN OF shade_step
+// (tray_kernel.hip), the same expressions in the same order on a plain path state
+// instead of the megakernel's Lane / end_path; a change to either belongs in both
+// (tests/test_gpu_query.py compares the two bit for bit). Returns true when the path
+// goes on with (org, dir), false when it ended with `color`.
+__device__ __forceinline__ bool query_shade(const KernelParams& p, const SceneView& sv, const QHit& h, uint32_t pixel,
+                                            uint32_t sample, uint32_t& bounce, D3& org, D3& dir, D3& thr, D3& color) {
+    const bool hit = h.ref >= 0;
+    // A hit at the last level ends the path black (RayColor(depth 0) is black).
+    const bool last = bounce + 1u >= (uint32_t)p.max_depth;
+    color = d3(0, 0, 0);
+    if (!hit) {  // AmbientLight.Hit (ray/objects.go:68-73)
+        const D3 ud = unit_lsq(dir, h.a);
+        const double t = 0.5 * (ud.y + 1.0);
+        const D3 bg_a = d3(p.bg_a.x, p.bg_a.y, p.bg_a.z), bg_b = d3(p.bg_b.x, p.bg_b.y, p.bg_b.z);
+        color = mul(thr, add(smul(bg_a, 1.0 - t), smul(bg_b, t)));
+        return false;
+    }
+    if (last) return false;
+    const double4 g = h.tree ? sv.bgeo[h.ref] : sv.geo[h.ref];
+    const MatRec m = h.tree ? sv.bmat[h.ref] : p.mat[h.ref];
+    const Block w = draw(p, pixel, sample, bounce, kPurposeScatter);
+    const double u0 = uniform(w.x0);
+    D3 ud = d3(0, 0, 0);
+    if (m.type != kLambertian) ud = unit_lsq(dir, h.a);
+    const D3 point = add(org, smul(dir, h.t));                                     // Ray.At (ray/ray.go:23-25)
+    const D3 outward = sdiv_rcp(sub(point, d3(g.x, g.y, g.z)), m.radius, m.rinv);  // ray/objects.go:100
+    const bool front = dot(dir, outward) < 0;                                      // SetFaceNormal (:19-26)
+    const D3 normal = neg_if(outward, !front);
+    bool scattered = true;
+    D3 new_dir;
+    D3 att = d3(m.albedo[0], m.albedo[1], m.albedo[2]);
+    const bool lambertian = m.type == kLambertian, dielectric = m.type == kDielectric;
+    const double cos_theta = go_min1(dot(neg(ud), normal));
+    const double z = 1.0 - 2.0 * u0;
+    const double sq = sqrt_cr(dielectric ? 1.0 - cos_theta * cos_theta : 1.0 - z * z);
+    D3 uv = d3(0, 0, 0);
+    if (lambertian || (m.type == kMetal && m.param > 0.0)) uv = unit_vector_from(z, sq, w.x1);
+    if (lambertian) {  // ray/materials.go:13-20
+        new_dir = add(normal, uv);
+        if (near_zero(new_dir)) new_dir = normal;
+    } else if (m.type == kMetal) {  // ray/materials.go:28-37
+        D3 reflected = reflect(ud, normal);
+        if (m.param > 0.0) reflected = add(reflected, smul(uv, m.param));
+        new_dir = reflected;
+        scattered = dot(new_dir, normal) > 0;
+    } else {  // Dielectric, ray/materials.go:44-64
+        att = d3(1.0, 1.0, 1.0);
+        const double ratio = front ? m.pinv : m.param;
+        const double sin_theta = sq;
+        const double r0 = front ? m.albedo[0] : m.albedo[1];
+        const bool do_reflect = ratio * sin_theta > 1.0 || reflectance(cos_theta, r0) > u0;
+        new_dir = do_reflect ? reflect(ud, normal) : refract(ud, normal, ratio);
+    }
+    if (!scattered) return false;  // absorbed -> black
+    thr = mul(thr, att);           // outer-first throughput product, as the megakernel
+    org = point;
+    dir = new_dir;
+    ++bounce;
+    return true;
+}
+
+// Scene.RayColor: one path per lane, the recursion as the megakernel's bounce loop.
+// Segments count the path's Scene.Hit calls. Five waves per SIMD: the budget of 96 VGPRs
+// costs no scratch and fewer scalar spills than the compiler's own 98 at four waves, and
+// measured 10 % faster on the C2 rays (DESIGN.md "Ray queries"); six waves spill to scratch.
+__global__ __launch_bounds__(kQueryBlock, 5) void ray_color_kernel(KernelParams p, QueryArgs q) {
+    const uint32_t i = blockIdx.x * kQueryBlock + threadIdx.x;
+    if (i >= q.n) return;
+    const SceneView sv = scene_view(p);
+    const QStack S = lane_stack();
+    D3 org = ray_origin(q.rays, i), dir = ray_direction(q.rays, i);
+    const uint32_t pixel = q.ids ? q.ids[2 * (size_t)i] : i;
+    const uint32_t sample = q.ids ? q.ids[2 * (size_t)i + 1] : 0u;
+    D3 thr = d3(1, 1, 1), color = d3(0, 0, 0);
+    uint32_t bounce = 0, segments = 0;
+    bool more = true;
+    while (more) {
+        ++segments;
+        const QHit h = query_hit(sv, S, q, org, dir, __builtin_inf());
+        more = query_shade(p, sv, h, pixel, sample, bounce, org, dir, thr, color);
+    }
+    double* o = static_cast<double*>(q.out) + (size_t)i * 3;
+    o[0] = color.x;
+    o[1] = color.y;
+    o[2] = color.z;
+    if (q.segments) q.segments[i] = segments;
+}
+
+// The stacks of one workgroup; the dynamic-LDS default limit (64 KB) bounds them.
+static size_t query_stack_bytes(int32_t stack_cap) { return (size_t)stack_cap * kQueryBlock * sizeof(uint32_t); }
+constexpr size_t kQueryLdsMax = 64 * 1024;
+
+hipError_t launch_camera_rays(KernelParams p, tray_ray* rays, uint32_t* ids, uint32_t n, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    p.div_tile_rows = make_fastdiv((uint32_t)std::max(p.tile_rows, 1));  // row_of
+    hipLaunchKernelGGL(camera_rays_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, p, rays, ids, n);
+    return hipGetLastError();
+}
+
+static QueryArgs query_args(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays, uint32_t n,
+                            size_t& lds) {
+    QueryArgs q{};
+    q.rays = rays;
+    q.n = n;
+    lds = query_stack_bytes(p.stack_cap);
+    q.use_bvh = use_bvh && p.n_nodes > 0 && lds <= kQueryLdsMax ? 1 : 0;
+    if (!q.use_bvh) lds = 0;
+    q.bound = bound;
+    q.t_end = __builtin_inf();
+    return q;
+}
+
+hipError_t launch_scene_hit(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays, uint32_t n,
+                            double t_end, tray_hit* hits, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    size_t lds = 0;
+    QueryArgs q = query_args(p, use_bvh, bound, rays, n, lds);
+    q.out = hits;
+    q.t_end = t_end;
+    hipLaunchKernelGGL(scene_hit_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), lds, stream, p,
+                       q);
+    return hipGetLastError();
+}
+
+hipError_t launch_ray_color(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays,
+                            const uint32_t* ids, uint32_t n, double* rgb, uint32_t* segments, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    size_t lds = 0;
+    QueryArgs q = query_args(p, use_bvh, bound, rays, n, lds);
+    q.ids = ids;
+    q.out = rgb;
+    q.segments = segments;
+    hipLaunchKernelGGL(ray_color_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), lds, stream, p,
+                       q);
+    return hipGetLastError();
+}
+
+}  // namespace tray

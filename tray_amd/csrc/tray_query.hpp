@@ -1,0 +1,33 @@
+// Internal launch interface between the C-ABI glue (tray_abi.hip) and the
+// ray-query kernels (tray_query.hip, include/tray_query.h). Not part of the
+// public ABI.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/tray_query.h"
+#include "tray_kernel.hpp"
+
+namespace tray {
+
+// The queries read a scene and a camera through the megakernel's KernelParams
+// (prepare_render's scene, camera, row-set and draw-key fields; the work queue,
+// sample buffer and every other per-launch workspace stay null: no query
+// touches one).
+
+// Camera.GetRay for the n = p.rows x p.width x p.spp samples of p's row set,
+// pass p.pass0; ids nullable.
+hipError_t launch_camera_rays(KernelParams p, tray_ray* rays, uint32_t* ids, uint32_t n, hipStream_t stream);
+
+// Scene.Hit(r, Interval{1e-6, t_end}) for n rays. use_bvh: rays whose origin
+// lies in [-bound, bound]^3 traverse the BVH, the rest (and every ray without
+// it) take the reference-order linear scan.
+hipError_t launch_scene_hit(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays, uint32_t n,
+                            double t_end, tray_hit* hits, hipStream_t stream);
+
+// Scene.RayColor(r, p.max_depth) for n rays under p.key; ids and segments nullable.
+hipError_t launch_ray_color(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays,
+                            const uint32_t* ids, uint32_t n, double* rgb, uint32_t* segments, hipStream_t stream);
+
+}  // namespace tray

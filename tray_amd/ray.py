@@ -13,6 +13,14 @@ against `ray.New(w, h)` / `(*Tracer).Render(scene)` reads the same here:
     Lambertian/Metal/Dielectric materials.go    Lambertian / Metal / Dielectric
     DefaultScene(), RichScene(rng) objects.go   DefaultScene(), RichScene(seed)
     DefaultBackground()         objects.go:106  DefaultBackground()
+    (*Camera).GetRay(...)       camera.go:113   Tracer.CameraRays(yStart, yEnd) -> (rays, ids), every sample's ray
+    (*Scene).Hit(r, iv, hr)     objects.go:37   Scene.Hit(origins, directions, interval) -> HIT_DTYPE array
+    (*Scene).RayColor(r, depth) objects.go:49   Scene.RayColor(origins, directions, depth, seed) -> (rgb, segments)
+
+The last three are batched (include/tray_query.h): arrays of rays in, arrays of
+results out, each one kernel launch on the scene's device copy, which the Scene
+keeps while its spheres and background do not change (a picking loop uploads
+once). They take numpy arrays and stage them through torch tensors.
 
 The hot loop (everything under RenderLines) runs in the gfx950 megakernel via
 tray_amd._lib; this module only applies the Go defaults and marshals data.
@@ -81,6 +89,58 @@ def DefaultBackground() -> AmbientLight:  # ray/objects.go:106-110
 class Scene:  # ray/objects.go:32-35
     Objects: list = field(default_factory=list)
     Background: AmbientLight = field(default_factory=AmbientLight)
+    _uploaded: dict = field(default_factory=dict, repr=False, compare=False)  # device -> (scene bytes, DeviceScene)
+
+    def _device_scene(self, device: int) -> "_lib.DeviceScene":
+        """The scene's copy on `device` for the batched queries: uploaded on first
+        use and again only when the spheres or the background have changed."""
+        arr = self.to_array()
+        bg = _background(self.Background)
+        key = arr.tobytes() + bytes(bg)
+        have = self._uploaded.get(device)
+        if have is not None and have[0] == key:
+            return have[1]
+        if have is not None:
+            have[1].release()
+        dev = _lib.DeviceScene(arr, bg, device)
+        self._uploaded[device] = (key, dev)
+        return dev
+
+    def Hit(self, origins, directions, interval=(1e-6, math.inf), device: int = 0) -> np.ndarray:  # ray/objects.go:37-46
+        """Scene.Hit for n rays ((n, 3) origins and directions) over Interval{1e-6,
+        interval[1]}: a _lib.HIT_DTYPE array (index -1: no hit). The interval
+        start is the renderer's FrontEpsilon.Start; any other raises."""
+        if float(interval[0]) != 1e-6:
+            raise _lib.TrayError(_lib.TRAY_ERR_INVALID_ARGUMENT,
+                                 "Scene.Hit: the interval start is fixed at 1e-6 (FrontEpsilon.Start, ray/vec3.go:218)")
+        torch, rays = _stage_rays(origins, directions, device)
+        n = rays.shape[0]
+        hits = torch.empty((n, _lib.HIT_DTYPE.itemsize // 8), dtype=torch.float64, device=rays.device)
+        dev = self._device_scene(device)
+        dev.hit_async(rays.data_ptr(), n, hits.data_ptr(), float(interval[1]),
+                      stream=torch.cuda.current_stream(rays.device).cuda_stream)
+        return hits.cpu().numpy().reshape(-1).view(_lib.HIT_DTYPE)
+
+    def RayColor(self, origins, directions, depth: int, seed: int, ids=None, device: int = 0):  # ray/objects.go:49-62
+        """Scene.RayColor(r, depth) for n rays: ((n, 3) float64 colours, (n,) uint32
+        Scene.Hit counts). ids ((n, 2) uint32, e.g. from Tracer.CameraRays): the
+        (pixel, sample word) whose scatter draws each ray takes under `seed`;
+        None: pixel = ray index, sample 0."""
+        torch, rays = _stage_rays(origins, directions, device)
+        n = rays.shape[0]
+        ids_t = None
+        if ids is not None:
+            ids_np = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            if ids_np.size != 2 * n:
+                raise ValueError("ids must hold a (pixel, sample) pair per ray")
+            ids_t = torch.from_numpy(ids_np.view(np.int32)).to(rays.device)
+        rgb = torch.empty((n, 3), dtype=torch.float64, device=rays.device)
+        seg = torch.empty((n,), dtype=torch.int32, device=rays.device)
+        dev = self._device_scene(device)
+        dev.ray_color_async(rays.data_ptr(), n, int(depth), int(seed), rgb.data_ptr(),
+                            ids_t.data_ptr() if ids_t is not None else None, seg.data_ptr(),
+                            stream=torch.cuda.current_stream(rays.device).cuda_stream)
+        return rgb.cpu().numpy(), seg.cpu().numpy().view(np.uint32)
 
     def to_array(self) -> np.ndarray:
         """Flatten to the C-ABI's tray_sphere array; unsupported objects raise
@@ -115,6 +175,18 @@ class Scene:  # ray/objects.go:32-35
                 mat = Dielectric(float(s["param"]))
             objs.append(Sphere(tuple(s["center"].tolist()), float(s["radius"]), mat))
         return Scene(objs, background or AmbientLight())
+
+
+def _stage_rays(origins, directions, device: int):
+    """(torch, an (n, 6) float64 tensor on `device` laid out as n x tray_ray)."""
+    import torch
+
+    o = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions must both be (n, 3)")
+    rays = np.ascontiguousarray(np.concatenate([o, d], axis=1))
+    return torch, torch.from_numpy(rays).to(f"cuda:{int(device)}")
 
 
 def _background(bg: AmbientLight) -> _lib.Background:
@@ -274,6 +346,28 @@ class Tracer:  # ray/tracer.go:25-36
         rgba = np.zeros((y1 - y0, self.width, 4), dtype=np.uint8)
         _lib.check(_lib.lib().tray_to_srgba(rgb.ctypes.data, rgb.shape[0] * rgb.shape[1], rgba.ctypes.data))
         self.imageData[y0:y1] = rgba
+
+    def CameraRays(self, yStart: int, yEnd: int, pass_: int = 0):  # ray/camera.go:113-142, ray/tracer.go:130-141
+        """Camera.GetRay for every sample of rows [yStart, yEnd): the rays RenderLines
+        traces there with the current (initialized) camera and fields, as a
+        _lib.RAY_DTYPE array of (yEnd - yStart) x width x NumRaysPerPixel rays (row,
+        column, sample order), and their (pixel, sample word) pairs as an (n, 2)
+        uint32 array for Scene.RayColor. Set Seed for rays that repeat."""
+        import torch
+
+        if self.Camera._state is None:
+            raise _lib.TrayError(_lib.TRAY_ERR_INVALID_ARGUMENT, "Camera.Initialize must be called first")
+        device = self.Devices[0] if self.Devices else self.Device
+        params = _lib.make_params(self.width, self.height, max(self.MaxDepth, 1), max(self.NumRaysPerPixel, 1),
+                                  self.RayRadius if self.RayRadius > 0 else 0.5, self._seed(), yStart, yEnd,
+                                  pass_=pass_)
+        n = _lib.camera_rays_count(params)
+        where = torch.device(f"cuda:{int(device)}")
+        rays = torch.empty((n, 6), dtype=torch.float64, device=where)
+        ids = torch.empty((n, 2), dtype=torch.int32, device=where)
+        _lib.camera_rays_async(self.Camera._state, params, rays.data_ptr(), ids.data_ptr(), device,
+                               torch.cuda.current_stream(where).cuda_stream)
+        return rays.cpu().numpy().reshape(-1).view(_lib.RAY_DTYPE), ids.cpu().numpy().view(np.uint32)
 
     def Render(self, scene: Scene | None) -> np.ndarray:  # ray/tracer.go:48-118
         scene = self._apply_defaults(scene)
