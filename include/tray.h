@@ -295,7 +295,8 @@ int tray_scene_release(tray_scene_t scene);
 /* How an uploaded scene is traversed (diagnostics; no reference counterpart). */
 typedef struct tray_scene_info {
     int32_t n_spheres;
-    int32_t has_bvh;      /* 0: every render uses the reference-order linear scan */
+    int32_t has_bvh;      /* 0: every render uses the reference-order linear scan (fewer than 16 spheres, a
+                           * NaN or infinite centre or radius, or a sphere reaching beyond +-2^28) */
     int32_t leaf_max;     /* spheres per BVH leaf (1, 2 or 4: the size whose LDS layout ranks best) */
     int32_t n_nodes;      /* 4-wide BVH nodes */
     int32_t n_leaves;
@@ -320,7 +321,8 @@ int tray_scene_get_info(tray_scene_t scene, tray_scene_info *out);
 typedef struct tray_render_plan {
     int32_t fixed_point_shift; /* k (0: FP64 sum in sample order) */
     int32_t acc_slots;         /* on-chip accumulators per wave (0: per-sample buffer) */
-    int32_t bvh;               /* 1: the BVH kernel; 0: the reference-order linear scan */
+    int32_t bvh;               /* 1: the BVH kernel; 0: the reference-order linear scan (no tree, the flag, a
+                                * camera outside the scene bound, or an infinite or NaN albedo) */
     int32_t lds_layout;        /* BVH: as tray_scene_info.lds_resident; linear scan: 1 geometry in LDS */
     int32_t stack_lds;         /* BVH: traversal stack entries per lane kept in LDS */
     int32_t reserved;          /* 0 */

@@ -56,8 +56,14 @@ struct Bvh {
     int32_t n_global = 0;         // spheres tested before the tree: the last n_global slots
 };
 
-// Returns false on non-finite input or a tree the kernel cannot index (the
-// caller then uses the linear scan).
+// The largest scene bound M (below) the FP32 slab test is conservative for:
+// beyond it a slab product can overflow to +-inf and cull a box the ray runs
+// through (derivation at the top of tray_bvh.cpp).
+constexpr double kBvhMaxBound = 0x1p28;
+
+// Returns false on input with a NaN or infinite coordinate or radius, on a
+// sphere box that reaches beyond +-kBvhMaxBound, or on a tree the kernel cannot
+// index (the caller then uses the linear scan).
 bool build_bvh(const tray_sphere* spheres, int32_t n, Bvh* out, int leaf_max = 1);
 // Build variants for offline comparison (tools/bvh_sim.cpp); the defaults are build_bvh's.
 struct BvhOptions {

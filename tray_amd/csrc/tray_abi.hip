@@ -228,7 +228,10 @@ struct tray_scene_s {
     tray::MatRec* mat;
     tray::V3 bg_a, bg_b;
     double max_att;  // max(1, |albedo| of every Lambertian/Metal sphere): bounds a path's throughput
-    // exact-culling BVH (absent for tiny or non-finite scenes)
+                     // (infinite when one of them is infinite or NaN: KernelParams::wild_att)
+    // exact-culling BVH (absent for tiny scenes, for scenes with a NaN or infinite
+    // coordinate or radius and for scenes that reach beyond +-kBvhMaxBound, bvh.hpp:
+    // those take the linear scan, and with no tree there are no candidate lists)
     bool has_bvh;
     double bvh_bound;
     int32_t n_nodes, n_slots, n_leaves, stack_cap, leaf_max, n_global;
@@ -587,6 +590,7 @@ static void scene_params(const tray_scene_s* sc, KernelParams& k) {
     k.leaves = sc->leaves;
     k.leaf_single = sc->leaf_max == 1 ? 1 : 0;
     k.stack_cap = sc->stack_cap;
+    k.wild_att = std::isfinite(sc->max_att) ? 0u : 1u;
 }
 
 // The camera and the draw key of `seed` in the kernel parameters (get_ray, draw).
@@ -655,7 +659,10 @@ static int prepare_render(tray_scene_t sc, const tray_camera* cam, const tray_pa
     for (int i = 0; i < 3; ++i) cam_extent = std::max(cam_extent, std::fabs(cam->position[i]));
     cam_extent += std::fabs(cam->defocus_u[0]) + std::fabs(cam->defocus_u[1]) + std::fabs(cam->defocus_u[2]) +
                   std::fabs(cam->defocus_v[0]) + std::fabs(cam->defocus_v[1]) + std::fabs(cam->defocus_v[2]);
-    use_bvh = sc->has_bvh && !(p->flags & TRAY_FLAG_LINEAR_SCAN) && cam_extent <= sc->bvh_bound;
+    // A scene with an infinite or NaN albedo renders through the linear scan: the
+    // one kernel instance that multiplies an ended path's black by its attenuations
+    // as Go's recursion does (tray_kernel.hip shade_step, kWild).
+    use_bvh = sc->has_bvh && !(p->flags & TRAY_FLAG_LINEAR_SCAN) && cam_extent <= sc->bvh_bound && k.wild_att == 0;
     return TRAY_OK;
 }
 

@@ -17,6 +17,24 @@
 // origin to satisfy |o| <= M (hit points lie inside the boxes; the camera is
 // checked at launch, else the linear scan is used).
 //
+// Range of M: the bound above is a relative-error argument, so it holds only
+// while no float in the slab test overflows. The kernel forms plane * inv and
+// org * inv with |plane|, |org| <= M (1 + 4e-6)(1 + u) and inv = 1/d for a
+// direction component clamped to |d| >= 1e-30 (trav_begin32), so |inv| <=
+// 1e30 (1 + 2u). A product beyond FLT_MAX = 3.4028e38 becomes +-inf, and
+// fma(plane, inv, -inf) is then the same infinity for the near and the far plane of
+// a box the ray runs through: the child is culled although the FP64 test hits
+// a sphere in it. The same happens without any small d once M itself exceeds
+// FLT_MAX: origins on a large sphere convert to +-inf next to finite boxes.
+// Every product stays finite iff M (1 + 4e-6)(1 + 3u) 1e30 <= FLT_MAX, i.e.
+// M <= 3.4028e8; kBvhMaxBound = 2^28 = 2.684e8 is the largest power of two
+// below that. There is no lower limit: M is at least 1, so the padding is at
+// least 4e-6 and a scene far smaller than that is one cluster of overlapping
+// boxes (every box is visited). NaN coordinates have no place in a box (min and
+// max ignore them), so a sphere with one is refused like an infinite one. Scenes
+// outside the range have no tree (build_bvh returns false) and take the
+// linear scan, which is the reference's own loop.
+//
 // Build: binned SAH over sphere centroids into a binary tree (object-median
 // splits once a branch gets deep, so depth stays bounded), then collapsed into
 // 4-wide nodes by repeatedly opening the largest-area inner child. Spheres
@@ -348,10 +366,11 @@ bool build_bvh_opts(const tray_sphere* s, int32_t n, Bvh* out, int leaf_max, con
             p.box.lo[k] = s[i].center[k] - r;
             p.box.hi[k] = s[i].center[k] + r;
             p.c[k] = s[i].center[k];
+            // !(x <= bound) also catches NaN, which std::max would drop
+            if (!(fabs(p.box.lo[k]) <= kBvhMaxBound) || !(fabs(p.box.hi[k]) <= kBvhMaxBound)) return false;
             m = std::max(m, std::max(fabs(p.box.lo[k]), fabs(p.box.hi[k])));
         }
         p.index = i;
-        if (!std::isfinite(m)) return false;
     }
     m = std::max(m, 1.0);
     B.pad = 4e-6 * m;

@@ -1024,13 +1024,21 @@ __device__ __forceinline__ uint64_t acc_retire(const KernelParams& p, const AccC
 // Written for a wave of lanes on different branches: the work several branches
 // need is done once, before them — the bounce's draw block and the unit
 // direction (sky, Metal, Dielectric).
-template <bool kStats, int kAcc, typename GeoAt, typename MatAt>
+template <bool kStats, int kAcc, bool kWild, typename GeoAt, typename MatAt>
 __device__ __forceinline__ bool shade_step(const KernelParams& p, Lane& L, int best, double closest,
                                            double dir_lsq, GeoAt geo_at, MatAt mat_at, Stats& st, const AccCtx& acc) {
     const bool hit = best >= 0;
     // A hit at the last level ends the path black whatever its material does
     // (RayColor(depth 0) is black), so no scatter is computed for it.
     const bool last = L.bounce + 1u >= (uint32_t)p.max_depth;
+    // The exception is a scene with an infinite or NaN albedo (kWild; KernelParams::wild_att).
+    // Go multiplies the black of an ended path by every attenuation above it
+    // (Mul(attenuation, RayColor(...)), ray/objects.go:56), the last level's too
+    // when its material scatters, and inf * 0 and NaN * 0 are NaN. In such a
+    // scene a last-level hit therefore scatters like any other hit and the
+    // black is multiplied (below). In every other scene those products are
+    // zeros and are not formed.
+    const bool blind = kWild ? false : last;  // a last-level hit whose scatter cannot show
     bool ends = !hit || last;
     // Issued first, for every lane (a miss reads a valid record it ignores), so
     // the L2 round trip of the shading record overlaps the FP64 work below
@@ -1043,13 +1051,13 @@ __device__ __forceinline__ bool shade_step(const KernelParams& p, Lane& L, int b
     // (nor a last-level hit): a wave whose shading lanes are all Lambertian hits
     // (a camera-ray pass of a diffuse pixel) skips the sqrt and three quotients.
     D3 ud = d3(0, 0, 0);
-    if (!hit || (!last && m.type != kLambertian)) ud = unit_lsq(L.dir, dir_lsq);  // dir_lsq = length_sq(L.dir)
+    if (!hit || (!blind && m.type != kLambertian)) ud = unit_lsq(L.dir, dir_lsq);  // dir_lsq = length_sq(L.dir)
     D3 color = d3(0, 0, 0);
     if (!hit) {  // AmbientLight.Hit (ray/objects.go:68-73)
         const double t = 0.5 * (ud.y + 1.0);
         const D3 bg_a = d3(p.bg_a.x, p.bg_a.y, p.bg_a.z), bg_b = d3(p.bg_b.x, p.bg_b.y, p.bg_b.z);
         color = mul(L.thr, add(smul(bg_a, 1.0 - t), smul(bg_b, t)));
-    } else if (!last) {
+    } else if (!blind) {
         const D3 point = add(L.org, smul(L.dir, closest));                             // Ray.At (ray/ray.go:23-25)
         const D3 outward = sdiv_rcp(sub(point, d3(g.x, g.y, g.z)), m.radius, m.rinv);  // ray/objects.go:100
         const bool front = dot(L.dir, outward) < 0;                                    // SetFaceNormal (:19-26)
@@ -1080,13 +1088,14 @@ __device__ __forceinline__ bool shade_step(const KernelParams& p, Lane& L, int b
             const bool do_reflect = ratio * sin_theta > 1.0 || reflectance(cos_theta, r0) > u0;
             new_dir = do_reflect ? reflect(ud, normal) : refract(ud, normal, ratio);
         }
-        if (scattered) {
+        if (scattered && (kWild ? !last : true)) {
             L.thr = mul(L.thr, att);
             L.org = point;
             L.dir = new_dir;
             ++L.bounce;
         } else {
-            ends = true;  // absorbed -> black
+            ends = true;  // absorbed, or scattered into depth 0 (wild only) -> black
+            if constexpr (kWild) color = smul(scattered ? mul(L.thr, att) : L.thr, 0.0);
         }
     }
     // Settle the shading-record loads here, on every path: vmcnt is one in-order
@@ -1308,8 +1317,12 @@ __host__ __device__ constexpr size_t bvh_stack_bytes(int32_t slots) { return (si
 // kAcc: on-chip fixed-point accumulation (end_path): 0 off, 1 one sum per 64-item chunk,
 // 2 one per pixel-pass of a chunk (r = 16, 32).
 // kSteps: node steps per loop iteration at most (kDeepSteps for deep trees, launch_render).
-template <int kLDS, bool kBVH, bool kStats, bool kSpill, bool kProg, int kAcc, int kSteps = TRAY_NODE_STEPS_MAX>
+// kWild: the instance for scenes with an infinite or NaN albedo (shade_step), linear scan only:
+// such a scene renders through the reference's own loop, and no other instance carries its code.
+template <int kLDS, bool kBVH, bool kStats, bool kSpill, bool kProg, int kAcc, int kSteps = TRAY_NODE_STEPS_MAX,
+          bool kWild = false>
 __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_SIMD : TRAY_WAVES_PER_SIMD) void render_kernel(KernelParams p) {
+    static_assert(!(kWild && (kBVH || kAcc != 0)), "kWild: linear scan, FP64 sums");
     extern __shared__ __attribute__((aligned(16))) double4 smem_all[];
     __attribute__((address_space(3))) Uniforms* uni_lds =
         (__attribute__((address_space(3))) Uniforms*)reinterpret_cast<Uniforms*>(smem_all);
@@ -1625,7 +1638,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 PROF_MATERIAL(0, cam_hit);
                 bool ended = false;
                 if (cam_hit) {
-                    if (shade_step<kStats, kAcc>(kp_fresh(), L, T.slot, T.closest, T.a, [&] { return sv.bgeo[max(T.slot, 0)]; },
+                    if (shade_step<kStats, kAcc, false>(kp_fresh(), L, T.slot, T.closest, T.a, [&] { return sv.bgeo[max(T.slot, 0)]; },
                                                  [&] { return sv.bmat[max(T.slot, 0)]; }, st, acc)) {
                         ++L.segments;
                         T.cur = kTravReady;  // set up by the begin step below
@@ -1686,7 +1699,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 ++L.segments;
                 double closest;
                 const int best = scene_hit_linear<TRAY_UNROLL, kStats>(sv, L.org, L.dir, closest, st);
-                ended = !shade_step<kStats, kAcc>(p, L, best, closest, length_sq(L.dir), [&] { return p.geo[max(best, 0)]; },  // NaN-padded: entry 0 exists
+                ended = !shade_step<kStats, kAcc, kWild>(p, L, best, closest, length_sq(L.dir), [&] { return p.geo[max(best, 0)]; },  // NaN-padded: entry 0 exists
                                                   [&] { return best >= 0 ? p.mat[best] : MatRec{}; }, st, acc);
             }
             if constexpr (kProg) count_progress(p, ended, L.j, lane, prog_cur, prog_cnt);
@@ -1833,7 +1846,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
 #ifdef TRAY_PROBE_SHADE64
                     TRAY_PROBE_F64(TRAY_PROBE_SHADE64)
 #endif
-                    if (shade_step<kStats, kAcc>(kp_fresh(), L, T.slot, T.closest, T.a, [&] { return sv.bgeo[max(T.slot, 0)]; },
+                    if (shade_step<kStats, kAcc, false>(kp_fresh(), L, T.slot, T.closest, T.a, [&] { return sv.bgeo[max(T.slot, 0)]; },
                                                  [&] { return sv.bmat[max(T.slot, 0)]; }, st, acc)) {
                         ++L.segments;
 #if defined(TRAY_STATS_GROUND) && !defined(TRAY_PROFILE)
@@ -2231,7 +2244,12 @@ hipError_t launch_to_srgba(const double* rgb, size_t n_pixels, uint32_t* rgba, c
 using KernelFn = void (*)(KernelParams);
 
 template <bool kBVH, bool kSpill, bool kStats, bool kProg, int kAcc, int kSteps>
-static KernelFn pick_kernel4(int lds_mode) {
+static KernelFn pick_kernel4(int lds_mode, bool wild) {
+    if constexpr (!kBVH && kAcc == 0) {
+        if (wild)
+            return lds_mode == 1 ? render_kernel<1, false, kStats, kSpill, kProg, 0, kSteps, true>
+                                 : render_kernel<0, false, kStats, kSpill, kProg, 0, kSteps, true>;
+    }
     if constexpr (kAcc == 2) {  // pixel-pass groups: only with the whole scene in LDS (launch_layout)
         (void)lds_mode;
         return render_kernel<1, kBVH, kStats, kSpill, kProg, kAcc, kSteps>;
@@ -2243,19 +2261,19 @@ static KernelFn pick_kernel4(int lds_mode) {
     }
 }
 template <bool kBVH, bool kSpill, bool kStats, bool kProg, int kAcc>
-static KernelFn pick_kernel3(int lds_mode, bool deep) {
+static KernelFn pick_kernel3(int lds_mode, bool deep, bool wild) {
     if constexpr (kBVH && !kSpill && kAcc != 2)
-        if (deep) return pick_kernel4<kBVH, kSpill, kStats, kProg, kAcc, kDeepSteps>(lds_mode);
-    return pick_kernel4<kBVH, kSpill, kStats, kProg, kAcc, TRAY_NODE_STEPS_MAX>(lds_mode);
+        if (deep) return pick_kernel4<kBVH, kSpill, kStats, kProg, kAcc, kDeepSteps>(lds_mode, wild);
+    return pick_kernel4<kBVH, kSpill, kStats, kProg, kAcc, TRAY_NODE_STEPS_MAX>(lds_mode, wild);
 }
 
 // Instrumentation: the stats instance counts segments and tests; the progress
 // instance feeds tray_render_progress; neither is ever timed by the bench.
 template <bool kBVH, bool kSpill, int kAcc>
-static KernelFn pick_kernel2(int lds_mode, bool stats, bool progress, bool deep) {
-    if (stats) return pick_kernel3<kBVH, kSpill, true, false, kAcc>(lds_mode, deep);
-    if (progress) return pick_kernel3<kBVH, kSpill, false, true, kAcc>(lds_mode, deep);
-    return pick_kernel3<kBVH, kSpill, false, false, kAcc>(lds_mode, deep);
+static KernelFn pick_kernel2(int lds_mode, bool stats, bool progress, bool deep, bool wild = false) {
+    if (stats) return pick_kernel3<kBVH, kSpill, true, false, kAcc>(lds_mode, deep, wild);
+    if (progress) return pick_kernel3<kBVH, kSpill, false, true, kAcc>(lds_mode, deep, wild);
+    return pick_kernel3<kBVH, kSpill, false, false, kAcc>(lds_mode, deep, wild);
 }
 
 // The next launch's work order from a counting launch's tile costs (one
@@ -2293,8 +2311,9 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(uint32_t* cost, uint32
 // On-chip accumulation is built for the BVH kernel with the whole stack on
 // chip (launch_layout grants accumulators only then); every other launch sums
 // through the per-sample buffer.
-static KernelFn pick_kernel(int lds_mode, bool bvh, bool stats, bool progress, bool spill, int acc, bool deep) {
-    if (!bvh) return pick_kernel2<false, false, 0>(lds_mode, stats, progress, false);
+static KernelFn pick_kernel(int lds_mode, bool bvh, bool stats, bool progress, bool spill, int acc, bool deep,
+                            bool wild) {
+    if (!bvh) return pick_kernel2<false, false, 0>(lds_mode, stats, progress, false, wild);
     if (spill) return pick_kernel2<true, true, 0>(lds_mode, stats, progress, false);
     if (acc == 2) return pick_kernel2<true, false, 2>(lds_mode, stats, progress, false);
     return acc == 1 ? pick_kernel2<true, false, 1>(lds_mode, stats, progress, deep)
@@ -2498,6 +2517,7 @@ hipError_t launch_render(KernelParams p, bool use_bvh, const LaunchPlan& plan, h
     p.acc_off = layout.acc_off;
     p.acc_rshift = layout.acc_rshift;
     if (use_bvh && p.stack_cap > p.stack_lds && !p.stack_ovf) return hipErrorInvalidValue;
+    if (p.wild_att != 0 && (use_bvh || p.acc_shift != 0)) return hipErrorInvalidValue;  // prepare_render's invariant
     // The caller sized p.samples from this plan (an invariant: the plan is decided once).
     const int32_t band_tiles = plan.band_tiles;
     if (plan.buffer_bytes > samples_bytes) return hipErrorInvalidValue;
@@ -2509,7 +2529,7 @@ hipError_t launch_render(KernelParams p, bool use_bvh, const LaunchPlan& plan, h
         deep = use_bvh && knob != 0;
     const KernelFn fn = pick_kernel(lds_mode, use_bvh, stats, p.progress != nullptr,
                                     use_bvh && p.stack_cap > p.stack_lds,
-                                    p.acc_slots <= 0 ? 0 : p.acc_rshift < 6u ? 2 : 1, deep);
+                                    p.acc_slots <= 0 ? 0 : p.acc_rshift < 6u ? 2 : 1, deep, p.wild_att != 0);
     const KernelFn resolve = pick_resolve(p);
     // Per-device, per-(kernel, LDS size) launch setup, cached.
     struct Setup {

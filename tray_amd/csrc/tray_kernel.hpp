@@ -149,6 +149,12 @@ struct KernelParams {
     // run dry and it holds at most this many paths, each of their segments is one scan of
     // every sphere by the whole wave instead of a one-lane traversal. 0: off.
     uint32_t coop_lanes;
+    // 1: some Lambertian or Metal albedo of the scene is infinite or NaN, so the black of
+    // an ended path is multiplied by the path's attenuations as Go's recursion does
+    // (inf * 0 = NaN; tray_kernel.hip shade_step). Such a scene renders through the
+    // linear scan's kWild instance and has no fixed-point sums (no colour bound).
+    // 0: those products are zeros and are not formed.
+    uint32_t wild_att;
 };
 
 struct LaunchPlan;

@@ -197,7 +197,8 @@ __device__ __forceinline__ bool query_shade(const KernelParams& p, const SceneVi
         color = mul(thr, add(smul(bg_a, 1.0 - t), smul(bg_b, t)));
         return false;
     }
-    if (last) return false;
+    const bool wild = p.wild_att != 0;  // an infinite or NaN attenuation in the scene (shade_step)
+    if (last && !wild) return false;
     const double4 g = h.tree ? sv.bgeo[h.ref] : sv.geo[h.ref];
     const MatRec m = h.tree ? sv.bmat[h.ref] : p.mat[h.ref];
     const Block w = draw(p, pixel, sample, bounce, kPurposeScatter);
@@ -233,7 +234,10 @@ __device__ __forceinline__ bool query_shade(const KernelParams& p, const SceneVi
         const bool do_reflect = ratio * sin_theta > 1.0 || reflectance(cos_theta, r0) > u0;
         new_dir = do_reflect ? reflect(ud, normal) : refract(ud, normal, ratio);
     }
-    if (!scattered) return false;  // absorbed -> black
+    if (!scattered || last) {  // absorbed, or scattered into depth 0 (wild only) -> black
+        if (wild) color = smul(scattered ? mul(thr, att) : thr, 0.0);
+        return false;
+    }
     thr = mul(thr, att);           // outer-first throughput product, as the megakernel
     org = point;
     dir = new_dir;
