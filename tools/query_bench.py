@@ -12,6 +12,12 @@ are counted in separate, untimed launches. Prints one JSON line:
 
     python tools/query_bench.py [--repeats 10] [--lib other/libtray_amd.so]
 
+The queries of include/tray_shade.h run in the same windows: the occlusion query
+(t_end = inf) beside the closest hit on the same camera rays, Material.Scatter on
+those rays' hit records, AmbientLight.Hit, and closest hit and occlusion again on
+a ray set that starts on surfaces (the scattered rays of the first bounce). Their
+figures, each with its min and max, go to --shade-out.
+
 --lib also times the hit and colour queries of another build of the library
 (tools/build_variants.sh), alternating with the in-tree build, and checks that
 its results are the same bits.
@@ -32,6 +38,8 @@ def main():
     ap.add_argument("--inner", type=int, default=20, help="launches per timed window")
     ap.add_argument("--rays-per-pixel", type=int, default=4)
     ap.add_argument("--lib", default=None, help="another build of libtray_amd.so to time beside the in-tree one")
+    ap.add_argument("--shade-out", default="profiles/shade_bench_c2.json",
+                    help="where (under the repository) the tray_shade.h figures go; '' writes none")
     args = ap.parse_args()
     import torch
 
@@ -68,6 +76,30 @@ def main():
                                                         ids.data_ptr(), None, stream=stream),
         "render": lambda: scenes["tree"].render_async(cam._state, params, frame.data_ptr(), None, stream),
     }
+    # include/tray_shade.h on the same rays: occlusion (t_end = inf) beside the closest hit,
+    # Material.Scatter on those rays' hit records, AmbientLight.Hit; and a second ray set that
+    # starts on surfaces, the scattered rays of the first bounce, for occlusion and closest hit.
+    jobs["camera_rays"]()
+    jobs["hit_bvh"]()
+    occ = torch.empty(n, dtype=torch.uint8, device="cuda")
+    scat = torch.empty((n, 10), dtype=torch.float64, device="cuda")
+    sky = torch.empty((n, 3), dtype=torch.float64, device="cuda")
+    scenes["tree"].scatter_async(rays.data_ptr(), hits["bvh"].data_ptr(), n, seed, scat.data_ptr(), ids.data_ptr(), 0,
+                                 stream)
+    rays1 = scat[scat.view(torch.int32)[:, 18] == 1][:, 3:9].contiguous()  # bounce 1: the scattered rays
+    n1 = len(rays1)
+    hits1 = torch.empty((n1, 8), dtype=torch.float64, device="cuda")
+    occ1 = torch.empty(n1, dtype=torch.uint8, device="cuda")
+    shade_jobs = {
+        "occluded": lambda: scenes["tree"].occluded_async(rays.data_ptr(), n, occ.data_ptr(), stream=stream),
+        "scatter": lambda: scenes["tree"].scatter_async(rays.data_ptr(), hits["bvh"].data_ptr(), n, seed,
+                                                        scat.data_ptr(), ids.data_ptr(), 0, stream),
+        "sky": lambda: _lib.background_hit_async(bg, rays.data_ptr(), n, sky.data_ptr(), 0, stream),
+        "hit_bvh_bounce1": lambda: scenes["tree"].hit_async(rays1.data_ptr(), n1, hits1.data_ptr(), stream=stream),
+        "occluded_bounce1": lambda: scenes["tree"].occluded_async(rays1.data_ptr(), n1, occ1.data_ptr(),
+                                                                   stream=stream),
+    }
+    jobs.update(shade_jobs)
     if args.lib:
         jobs["hit_bvh_other"] = lambda: scenes["other"].hit_async(rays.data_ptr(), n, hits["other"].data_ptr(),
                                                                   stream=stream)
@@ -101,6 +133,9 @@ def main():
     assert torch.equal(hits["bvh"], hits["linear"]), "BVH and linear-scan hits differ"
     if args.lib:
         assert torch.equal(hits["bvh"], hits["other"]) and torch.equal(rgb["tree"], rgb["other"]), "--lib differs"
+    index, index1 = hits["bvh"].view(torch.int32)[:, 14], hits1.view(torch.int32)[:, 14]
+    assert torch.equal(occ != 0, index >= 0) and torch.equal(occ1 != 0, index1 >= 0), "occlusion is not index >= 0"
+    occluded, occluded1 = int(occ.sum().item()), int(occ1.sum().item())
     for s in scenes.values():
         s.release()
 
@@ -123,6 +158,25 @@ def main():
         out["other_hit_bvh_mrays_s"] = round(n / ms["hit_bvh_other"] / 1e3, 1)
         out["other_color_msegments_s"] = round(color_segments / ms["color_other"] / 1e3, 1)
     print(json.dumps(out))
+    if args.shade_out:
+        names = ["hit_bvh"] + list(shade_jobs)
+        shade = {
+            "scene": out["scene"], "width": W, "height": H, "rays_per_pixel": r, "rays": n, "rays_occluded": occluded,
+            "bounce1_rays": n1, "bounce1_rays_occluded": occluded1, "repeats": args.repeats,
+            "launches_per_window": args.inner,
+            "ms": {k: out["ms"][k] for k in names},
+            "ms_min_max": {k: out["ms_min_max"][k] for k in names},
+            "occluded_over_hit_bvh": round(ms["occluded"] / ms["hit_bvh"], 3),
+            "occluded_over_hit_bvh_bounce1": round(ms["occluded_bounce1"] / ms["hit_bvh_bounce1"], 3),
+            "scatter_mrays_s": round(n / ms["scatter"] / 1e3, 1),
+            "sky_mrays_s": round(n / ms["sky"] / 1e3, 1),
+            "code_object_sha256": out["code_object_sha256"],
+        }
+        path = os.path.join(ROOT, args.shade_out)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(shade, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":

@@ -185,6 +185,27 @@ class Hit(ctypes.Structure):
 
 assert ctypes.sizeof(Ray) == 48 and ctypes.sizeof(Hit) == 64
 
+# Every symbol include/tray_shade.h declares (Material.Scatter, AmbientLight.Hit and the
+# occlusion query; in neither EXPORTS nor QUERY_EXPORTS).
+SHADE_EXPORTS = (
+    "tray_shade_version",
+    "tray_scatter_async",
+    "tray_background_hit_async",
+    "tray_scene_occluded_async",
+)
+
+# tray_scatter (include/tray_shade.h) as a numpy structured dtype, C layout.
+SCATTER_DTYPE = np.dtype([("attenuation", "<f8", (3,)), ("ray", RAY_DTYPE), ("scattered", "<i4"), ("reserved", "<i4")])
+assert SCATTER_DTYPE.itemsize == 80 and SCATTER_DTYPE.fields["scattered"][1] == 72
+
+
+class Scatter(ctypes.Structure):
+    """tray_scatter."""
+    _fields_ = [("attenuation", _d3), ("ray", Ray), ("scattered", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(Scatter) == 80 and Scatter.scattered.offset == 72
+
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
 DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear")
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
@@ -270,6 +291,11 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.tray_camera_rays_async.argtypes = [ctypes.POINTER(CameraState), ctypes.POINTER(Params), i32, vp, vp, vp]
         L.tray_scene_hit_async.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_double, i32, vp, vp]
         L.tray_ray_color_async.argtypes = [vp, vp, vp, ctypes.c_int64, i32, ctypes.c_uint64, i32, vp, vp, vp]
+    if hasattr(L, "tray_shade_version"):  # include/tray_shade.h; absent from older builds (A/B tools)
+        L.tray_shade_version.restype = i32
+        L.tray_scatter_async.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64, vp, vp]
+        L.tray_background_hit_async.argtypes = [ctypes.POINTER(Background), vp, ctypes.c_int64, vp, i32, vp]
+        L.tray_scene_occluded_async.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_double, i32, vp, vp]
     if hasattr(L, "tray_debug_set"):  # absent from older builds (A/B tools)
         L.tray_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
         L.tray_debug_clear.argtypes = [ctypes.c_char_p]
@@ -490,6 +516,12 @@ def camera_rays_async(camera: CameraState, params: Params, rays_ptr: int, ids_pt
     check(lib().tray_camera_rays_async(ctypes.byref(camera), ctypes.byref(params), device, rays_ptr, ids_ptr, stream))
 
 
+def background_hit_async(background: Background, rays_ptr: int, n: int, rgb_ptr: int, device: int = 0,
+                         stream: int | None = None) -> None:
+    """tray_background_hit_async: AmbientLight.Hit for n device rays -> n x 3 f64. Needs no scene."""
+    check(lib().tray_background_hit_async(ctypes.byref(background), rays_ptr, int(n), rgb_ptr, device, stream))
+
+
 class DeviceScene:
     """A scene uploaded once to one device (tray_scene_upload); render many times,
     from any thread and on any streams: each render runs in a launch context of
@@ -545,6 +577,24 @@ class DeviceScene:
         (+ n x uint32 Scene.Hit counts); ids: the (pixel, sample word) pair of each ray's draws."""
         rc = self.L.tray_ray_color_async(self.handle, rays_ptr, ids_ptr, int(n), int(max_depth),
                                          int(seed) & (2**64 - 1), int(flags), rgb_ptr, segments_ptr, stream)
+        if rc != TRAY_OK:
+            raise TrayError(rc, self.L.tray_last_error().decode())
+
+    def scatter_async(self, rays_ptr: int, hits_ptr: int, n: int, seed: int, out_ptr: int,
+                      ids_ptr: int | None = None, bounce: int = 0, stream: int | None = None) -> None:
+        """tray_scatter_async: hits[i].Mat.Scatter(rays[i], hits[i]) for n device (ray, record) pairs
+        -> n x tray_scatter; ids: the (pixel, sample word) pair of each ray's draws at `bounce`."""
+        rc = self.L.tray_scatter_async(self.handle, rays_ptr, hits_ptr, ids_ptr, int(n), int(bounce),
+                                       int(seed) & (2**64 - 1), out_ptr, stream)
+        if rc != TRAY_OK:
+            raise TrayError(rc, self.L.tray_last_error().decode())
+
+    def occluded_async(self, rays_ptr: int, n: int, out_ptr: int, t_end: float = float("inf"),
+                       t_ends_ptr: int | None = None, flags: int = 0, stream: int | None = None) -> None:
+        """tray_scene_occluded_async: one byte per device ray, 1 iff a root lies in (1e-6, end);
+        end = t_ends_ptr[i] (n x f64) when given, else t_end."""
+        rc = self.L.tray_scene_occluded_async(self.handle, rays_ptr, t_ends_ptr, int(n), float(t_end), int(flags),
+                                              out_ptr, stream)
         if rc != TRAY_OK:
             raise TrayError(rc, self.L.tray_last_error().decode())
 

@@ -962,6 +962,59 @@ int tray_ray_color_async(tray_scene_t sc, const tray_ray* rays_device, const uin
     return TRAY_OK;
 }
 
+// ---- scatter, sky and occlusion queries (include/tray_shade.h) -------------------
+int32_t tray_shade_version(void) { return TRAY_SHADE_VERSION; }
+
+int tray_scatter_async(tray_scene_t sc, const tray_ray* rays_device, const tray_hit* hits_device,
+                       const uint32_t* ids_device, int64_t n, uint32_t bounce, uint64_t seed,
+                       tray_scatter* out_device, void* stream) {
+    int rc = validate_query(sc, rays_device, n, 0, out_device);
+    if (rc) return rc;
+    if (n > 0 && !hits_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null hit buffer");
+    if (n == 0) return TRAY_OK;
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    key_params(seed, k);
+    TRAY_HIP(hipSetDevice(sc->device));
+    TRAY_HIP(launch_scatter(k, rays_device, hits_device, ids_device, (uint32_t)n, bounce, out_device,
+                            static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
+int tray_background_hit_async(const tray_background* bg, const tray_ray* rays_device, int64_t n, double* rgb_device,
+                              int32_t device, void* stream) {
+    if (n < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative ray count");
+    if (n > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 rays in one query");
+    if (n > 0 && !rays_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null ray buffer");
+    if (n > 0 && !rgb_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null result buffer");
+    if (!bg) return fail(TRAY_ERR_INVALID_ARGUMENT, "null background");
+    if (n == 0) return TRAY_OK;
+    const int rc = device_usable(device);
+    if (rc) return rc;
+    TRAY_HIP(hipSetDevice(device));
+    TRAY_HIP(launch_background_hit(V3{bg->color_a[0], bg->color_a[1], bg->color_a[2]},
+                                   V3{bg->color_b[0], bg->color_b[1], bg->color_b[2]}, rays_device, (uint32_t)n,
+                                   rgb_device, static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
+int tray_scene_occluded_async(tray_scene_t sc, const tray_ray* rays_device, const double* t_end_device, int64_t n,
+                              double t_end, int32_t flags, uint8_t* occluded_device, void* stream) {
+    if (t_end != t_end) return fail(TRAY_ERR_INVALID_ARGUMENT, "t_end is NaN");
+    int rc = validate_query(sc, rays_device, n, flags, occluded_device);
+    if (rc) return rc;
+    if (n == 0) return TRAY_OK;
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    TRAY_HIP(hipSetDevice(sc->device));
+    TRAY_HIP(launch_scene_occluded(k, sc->has_bvh && !(flags & TRAY_FLAG_LINEAR_SCAN), sc->bvh_bound, rays_device,
+                                   t_end_device, (uint32_t)n, t_end, occluded_device,
+                                   static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
 static hipError_t grow(void** buf, size_t* have, size_t bytes) {
     if (*have >= bytes) return hipSuccess;
     if (*buf) (void)hipFree(*buf);

@@ -2,16 +2,17 @@
 // (include/tray_query.h): Camera.GetRay (ray/camera.go:113-142), Scene.Hit
 // (ray/objects.go:37-46, Sphere.Hit :81-104) and Scene.RayColor
 // (ray/objects.go:49-62) as kernels of their own, one ray (sample, path) per
-// lane.
+// lane; and (include/tray_shade.h) Material.Scatter (ray/materials.go:13-64),
+// AmbientLight.Hit (ray/objects.go:68-73) and the occlusion query, the same way.
 //
 // The arithmetic is the megakernel's, not a restatement of it: this file
 // includes tray_kernel.hip's device functions (get_ray, camera_block, draw,
 // quad, test_geo, trav_globals, trav_begin32, trav_node, trav_leaf,
 // scene_hit_linear, unit_lsq, sdiv_rcp, reflect, refract, ...) and leaves its
 // kernels and host side out. The one exception is the scatter step
-// (query_shade below), the twin of shade_step: that function is tied to the
-// megakernel's lane state and pixel sums, and factoring the arithmetic out of it
-// would have changed the product instances ("Ray queries").
+// (scatter_step and query_shade below), the twin of shade_step: that function is
+// tied to the megakernel's lane state and pixel sums, and factoring the arithmetic
+// out of it would have changed the product instances ("Ray queries").
 // Compiled with -ffp-contract=off like every other unit.
 
 #define TRAY_DEVICE_FUNCTIONS_ONLY
@@ -120,6 +121,41 @@ __device__ __forceinline__ QHit query_hit(const SceneView& sv, const QStack& S, 
     return h;
 }
 
+// "Does query_hit(..., t_end) hold a hit?" without finding the closest one: query_hit's
+// algorithm, the same per-ray choice of BVH or scan included, with an early exit. Under
+// the any-order rule a root is accepted only inside (1e-6, current closest), and the
+// culling distance starts at t_end with no hit held, so the first accepted root already
+// lies in (1e-6, t_end): the traversal stops there. What it would have gone on to find
+// is a closer root of the same interval, which cannot change the answer. A hit among the
+// out-of-tree spheres below t_end answers before the tree is entered.
+__device__ __forceinline__ bool query_occluded(const SceneView& sv, const QStack& S, const QueryArgs& q, const D3& org,
+                                               const D3& dir, double t_end) {
+    const double a = length_sq(dir);
+    const double M = q.bound;
+    const bool inside = __builtin_fabs(org.x) <= M && __builtin_fabs(org.y) <= M && __builtin_fabs(org.z) <= M;
+    const bool tree = q.use_bvh != 0 && inside && a >= 1e-30 && a <= 1e30;
+    if (!(t_end > 1e-6)) return false;  // an empty interval (a NaN end included) surrounds no root
+    if (tree) {
+        Trav T;
+        T.tlim = __builtin_inff();
+        trav_globals(T, sv, org, dir);
+        if (T.closest < t_end) return true;
+        T.closest = t_end;
+        T.slot = -1;
+        trav_begin32(T, sv, org, dir);
+        uint32_t tested;
+        while (T.cur != kBvhNone && T.slot < 0) {
+            if (is_trav(T.cur)) trav_node(T, sv, S, tested);
+            else trav_leaf(T, sv, S, org, dir, tested);
+        }
+        return T.slot >= 0;
+    }
+    Stats st;
+    double closest;
+    const int best = scene_hit_linear<TRAY_UNROLL, false>(sv, org, dir, closest, st);
+    return best >= 0 && closest < t_end;
+}
+
 __device__ __forceinline__ QStack lane_stack() {
     extern __shared__ __attribute__((aligned(16))) uint32_t query_stacks[];
     return QStack{(__attribute__((address_space(3))) uint32_t*)query_stacks + threadIdx.x};
@@ -179,39 +215,25 @@ __global__ __launch_bounds__(kQueryBlock) void scene_hit_kernel(KernelParams p, 
     o->front_face = front ? 1 : 0;
 }
 
-// One recursion level of RayColor after Scene.Hit gave `h`: THE TWIN OF shade_step
-// (tray_kernel.hip), the same expressions in the same order on a plain path state
-// instead of the megakernel's Lane / end_path; a change to either belongs in both
-// (tests/test_gpu_query.py compares the two bit for bit). Returns true when the path
-// goes on with (org, dir), false when it ended with `color`.
-__device__ __forceinline__ bool query_shade(const KernelParams& p, const SceneView& sv, const QHit& h, uint32_t pixel,
-                                            uint32_t sample, uint32_t& bounce, D3& org, D3& dir, D3& thr, D3& color) {
-    const bool hit = h.ref >= 0;
-    // A hit at the last level ends the path black (RayColor(depth 0) is black).
-    const bool last = bounce + 1u >= (uint32_t)p.max_depth;
-    color = d3(0, 0, 0);
-    if (!hit) {  // AmbientLight.Hit (ray/objects.go:68-73)
-        const D3 ud = unit_lsq(dir, h.a);
-        const double t = 0.5 * (ud.y + 1.0);
-        const D3 bg_a = d3(p.bg_a.x, p.bg_a.y, p.bg_a.z), bg_b = d3(p.bg_b.x, p.bg_b.y, p.bg_b.z);
-        color = mul(thr, add(smul(bg_a, 1.0 - t), smul(bg_b, t)));
-        return false;
-    }
-    const bool wild = p.wild_att != 0;  // an infinite or NaN attenuation in the scene (shade_step)
-    if (last && !wild) return false;
-    const double4 g = h.tree ? sv.bgeo[h.ref] : sv.geo[h.ref];
-    const MatRec m = h.tree ? sv.bmat[h.ref] : p.mat[h.ref];
+// Material.Scatter (ray/materials.go:13-64) of a ray with direction `dir` (a = |dir|^2) at a
+// hit whose record has `normal` and `front`: the draws of (pixel, sample, bounce, purpose 3),
+// then Lambertian, Metal or Dielectric. Returns didScatter and leaves the scattered
+// direction in `new_dir` and the attenuation in `att`; the scattered ray's origin is the
+// record's point, which the caller has. THE TWIN OF the same lines of shade_step
+// (tray_kernel.hip), which is tied to the megakernel's Lane: the same expressions in the
+// same order, and a change to either belongs in both (tests/test_gpu_query.py compares the
+// two bit for bit through query_shade, tests/test_gpu_shade.py this function with the
+// oracle). The one copy on the query side: query_shade (normal computed from the sphere)
+// and scatter_kernel (normal read from the caller's record) both call it.
+__device__ __forceinline__ bool scatter_step(const KernelParams& p, const MatRec& m, uint32_t pixel, uint32_t sample,
+                                             uint32_t bounce, const D3& dir, double a, const D3& normal, bool front,
+                                             D3& new_dir, D3& att) {
     const Block w = draw(p, pixel, sample, bounce, kPurposeScatter);
     const double u0 = uniform(w.x0);
     D3 ud = d3(0, 0, 0);
-    if (m.type != kLambertian) ud = unit_lsq(dir, h.a);
-    const D3 point = add(org, smul(dir, h.t));                                     // Ray.At (ray/ray.go:23-25)
-    const D3 outward = sdiv_rcp(sub(point, d3(g.x, g.y, g.z)), m.radius, m.rinv);  // ray/objects.go:100
-    const bool front = dot(dir, outward) < 0;                                      // SetFaceNormal (:19-26)
-    const D3 normal = neg_if(outward, !front);
+    if (m.type != kLambertian) ud = unit_lsq(dir, a);
     bool scattered = true;
-    D3 new_dir;
-    D3 att = d3(m.albedo[0], m.albedo[1], m.albedo[2]);
+    att = d3(m.albedo[0], m.albedo[1], m.albedo[2]);
     const bool lambertian = m.type == kLambertian, dielectric = m.type == kDielectric;
     const double cos_theta = go_min1(dot(neg(ud), normal));
     const double z = 1.0 - 2.0 * u0;
@@ -234,6 +256,36 @@ __device__ __forceinline__ bool query_shade(const KernelParams& p, const SceneVi
         const bool do_reflect = ratio * sin_theta > 1.0 || reflectance(cos_theta, r0) > u0;
         new_dir = do_reflect ? reflect(ud, normal) : refract(ud, normal, ratio);
     }
+    return scattered;
+}
+
+// One recursion level of RayColor after Scene.Hit gave `h`: the twin of shade_step
+// (tray_kernel.hip) on a plain path state instead of the megakernel's Lane / end_path,
+// with the material arithmetic in scatter_step (above). Returns true when the path
+// goes on with (org, dir), false when it ended with `color`.
+__device__ __forceinline__ bool query_shade(const KernelParams& p, const SceneView& sv, const QHit& h, uint32_t pixel,
+                                            uint32_t sample, uint32_t& bounce, D3& org, D3& dir, D3& thr, D3& color) {
+    const bool hit = h.ref >= 0;
+    // A hit at the last level ends the path black (RayColor(depth 0) is black).
+    const bool last = bounce + 1u >= (uint32_t)p.max_depth;
+    color = d3(0, 0, 0);
+    if (!hit) {  // AmbientLight.Hit (ray/objects.go:68-73)
+        const D3 ud = unit_lsq(dir, h.a);
+        const double t = 0.5 * (ud.y + 1.0);
+        const D3 bg_a = d3(p.bg_a.x, p.bg_a.y, p.bg_a.z), bg_b = d3(p.bg_b.x, p.bg_b.y, p.bg_b.z);
+        color = mul(thr, add(smul(bg_a, 1.0 - t), smul(bg_b, t)));
+        return false;
+    }
+    const bool wild = p.wild_att != 0;  // an infinite or NaN attenuation in the scene (shade_step)
+    if (last && !wild) return false;
+    const double4 g = h.tree ? sv.bgeo[h.ref] : sv.geo[h.ref];
+    const MatRec m = h.tree ? sv.bmat[h.ref] : p.mat[h.ref];
+    const D3 point = add(org, smul(dir, h.t));                                     // Ray.At (ray/ray.go:23-25)
+    const D3 outward = sdiv_rcp(sub(point, d3(g.x, g.y, g.z)), m.radius, m.rinv);  // ray/objects.go:100
+    const bool front = dot(dir, outward) < 0;                                      // SetFaceNormal (:19-26)
+    const D3 normal = neg_if(outward, !front);
+    D3 new_dir, att;
+    const bool scattered = scatter_step(p, m, pixel, sample, bounce, dir, h.a, normal, front, new_dir, att);
     if (!scattered || last) {  // absorbed, or scattered into depth 0 (wild only) -> black
         if (wild) color = smul(scattered ? mul(thr, att) : thr, 0.0);
         return false;
@@ -270,6 +322,66 @@ __global__ __launch_bounds__(kQueryBlock, 5) void ray_color_kernel(KernelParams 
     o[1] = color.y;
     o[2] = color.z;
     if (q.segments) q.segments[i] = segments;
+}
+
+// Material.Scatter (include/tray_shade.h): one record per lane. Point, normal, face and
+// sphere index are the RECORD's (the Go method reads rec, ray/materials.go:13-64), not
+// recomputed from the sphere; the material is the list-order record of `index`. A record
+// that is no hit of this scene (index outside [0, n)) reads no sphere and is not scattered.
+__global__ __launch_bounds__(kQueryBlock) void scatter_kernel(KernelParams p, const tray_ray* rays,
+                                                              const tray_hit* hits, const uint32_t* ids,
+                                                              tray_scatter* out, uint32_t n, uint32_t bounce) {
+    const uint32_t i = blockIdx.x * kQueryBlock + threadIdx.x;
+    if (i >= n) return;
+    const tray_hit* rec = hits + i;
+    const int32_t index = rec->index;
+    bool scattered = false;
+    D3 point = d3(0, 0, 0), new_dir = d3(0, 0, 0), att = d3(0, 0, 0);
+    if ((uint32_t)index < (uint32_t)p.n) {
+        const MatRec m = p.mat[index];
+        const D3 dir = ray_direction(rays, i);
+        const D3 normal = d3(rec->normal[0], rec->normal[1], rec->normal[2]);
+        const uint32_t pixel = ids ? ids[2 * (size_t)i] : i;
+        const uint32_t sample = ids ? ids[2 * (size_t)i + 1] : 0u;
+        scattered = scatter_step(p, m, pixel, sample, bounce, dir, length_sq(dir), normal, rec->front_face != 0,
+                                 new_dir, att);
+        point = d3(rec->point[0], rec->point[1], rec->point[2]);
+    }
+    if (!scattered) point = new_dir = att = d3(0, 0, 0);  // absorbed or no hit: every field zero
+    tray_scatter* o = out + i;
+    o->attenuation[0] = att.x, o->attenuation[1] = att.y, o->attenuation[2] = att.z;
+    o->ray.origin[0] = point.x, o->ray.origin[1] = point.y, o->ray.origin[2] = point.z;
+    o->ray.direction[0] = new_dir.x, o->ray.direction[1] = new_dir.y, o->ray.direction[2] = new_dir.z;
+    o->scattered = scattered ? 1 : 0;
+    o->reserved = 0;
+}
+
+// AmbientLight.Hit (ray/objects.go:68-73): query_shade's miss branch without the throughput.
+__global__ __launch_bounds__(kQueryBlock) void background_hit_kernel(V3 a, V3 b, const tray_ray* rays, double* rgb,
+                                                                     uint32_t n) {
+    const uint32_t i = blockIdx.x * kQueryBlock + threadIdx.x;
+    if (i >= n) return;
+    const D3 dir = ray_direction(rays, i);
+    const D3 ud = unit_lsq(dir, length_sq(dir));
+    const double t = 0.5 * (ud.y + 1.0);
+    const D3 color = add(smul(d3(a.x, a.y, a.z), 1.0 - t), smul(d3(b.x, b.y, b.z), t));
+    double* o = rgb + (size_t)i * 3;
+    o[0] = color.x;
+    o[1] = color.y;
+    o[2] = color.z;
+}
+
+// The occlusion query: one ray per lane, one byte out. t_ends (nullable) holds a
+// per-ray Interval.End, else q.t_end serves every ray.
+__global__ __launch_bounds__(kQueryBlock) void scene_occluded_kernel(KernelParams p, QueryArgs q,
+                                                                     const double* t_ends) {
+    const uint32_t i = blockIdx.x * kQueryBlock + threadIdx.x;
+    if (i >= q.n) return;
+    const SceneView sv = scene_view(p);
+    const QStack S = lane_stack();
+    const D3 org = ray_origin(q.rays, i), dir = ray_direction(q.rays, i);
+    const double t_end = t_ends ? t_ends[i] : q.t_end;
+    static_cast<uint8_t*>(q.out)[i] = query_occluded(sv, S, q, org, dir, t_end) ? 1 : 0;
 }
 
 // The stacks of one workgroup; the dynamic-LDS default limit (64 KB) bounds them.
@@ -318,6 +430,35 @@ hipError_t launch_ray_color(const KernelParams& p, bool use_bvh, double bound, c
     q.segments = segments;
     hipLaunchKernelGGL(ray_color_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), lds, stream, p,
                        q);
+    return hipGetLastError();
+}
+
+hipError_t launch_scatter(const KernelParams& p, const tray_ray* rays, const tray_hit* hits, const uint32_t* ids,
+                          uint32_t n, uint32_t bounce, tray_scatter* out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(scatter_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), 0, stream, p,
+                       rays, hits, ids, out, n, bounce);
+    return hipGetLastError();
+}
+
+hipError_t launch_background_hit(V3 color_a, V3 color_b, const tray_ray* rays, uint32_t n, double* rgb,
+                                 hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(background_hit_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), 0, stream,
+                       color_a, color_b, rays, rgb, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_scene_occluded(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays,
+                                 const double* t_ends, uint32_t n, double t_end, uint8_t* occluded,
+                                 hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    size_t lds = 0;
+    QueryArgs q = query_args(p, use_bvh, bound, rays, n, lds);
+    q.out = occluded;
+    q.t_end = t_end;
+    hipLaunchKernelGGL(scene_occluded_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), lds,
+                       stream, p, q, t_ends);
     return hipGetLastError();
 }
 

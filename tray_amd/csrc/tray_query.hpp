@@ -1,12 +1,12 @@
 // Internal launch interface between the C-ABI glue (tray_abi.hip) and the
-// ray-query kernels (tray_query.hip, include/tray_query.h). Not part of the
-// public ABI.
+// ray-query kernels (tray_query.hip, include/tray_query.h and tray_shade.h).
+// Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/tray_query.h"
+#include "../../include/tray_shade.h"  // includes tray_query.h
 #include "tray_kernel.hpp"
 
 namespace tray {
@@ -29,5 +29,21 @@ hipError_t launch_scene_hit(const KernelParams& p, bool use_bvh, double bound, c
 // Scene.RayColor(r, p.max_depth) for n rays under p.key; ids and segments nullable.
 hipError_t launch_ray_color(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays,
                             const uint32_t* ids, uint32_t n, double* rgb, uint32_t* segments, hipStream_t stream);
+
+// include/tray_shade.h.
+// Material.Scatter of n (ray, record) pairs at `bounce` under p.key (scene, material and
+// draw-key fields of p); ids nullable.
+hipError_t launch_scatter(const KernelParams& p, const tray_ray* rays, const tray_hit* hits, const uint32_t* ids,
+                          uint32_t n, uint32_t bounce, tray_scatter* out, hipStream_t stream);
+
+// AmbientLight{color_a, color_b}.Hit for n rays: 3 doubles per ray. Needs no scene.
+hipError_t launch_background_hit(V3 color_a, V3 color_b, const tray_ray* rays, uint32_t n, double* rgb,
+                                 hipStream_t stream);
+
+// occluded[i] = launch_scene_hit(..., end_i, ...) would report a hit, with end_i =
+// t_ends[i] (t_ends nullable: t_end). use_bvh and bound as for launch_scene_hit.
+hipError_t launch_scene_occluded(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays,
+                                 const double* t_ends, uint32_t n, double t_end, uint8_t* occluded,
+                                 hipStream_t stream);
 
 }  // namespace tray

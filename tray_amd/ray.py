@@ -16,8 +16,11 @@ against `ray.New(w, h)` / `(*Tracer).Render(scene)` reads the same here:
     (*Camera).GetRay(...)       camera.go:113   Tracer.CameraRays(yStart, yEnd) -> (rays, ids), every sample's ray
     (*Scene).Hit(r, iv, hr)     objects.go:37   Scene.Hit(origins, directions, interval) -> HIT_DTYPE array
     (*Scene).RayColor(r, depth) objects.go:49   Scene.RayColor(origins, directions, depth, seed) -> (rgb, segments)
+    Material.Scatter(r, rec)    materials.go:13 Scene.Scatter(origins, directions, hits, seed) -> SCATTER_DTYPE array
+    AmbientLight.Hit(r)         objects.go:68   AmbientLight.Hit(directions) -> (n, 3) colours
+    (no Go counterpart)                         Scene.Occluded(origins, directions, t_end) -> (n,) bool
 
-The last three are batched (include/tray_query.h): arrays of rays in, arrays of
+The last six are batched (include/tray_query.h, tray_shade.h): arrays of rays in, arrays of
 results out, each one kernel launch on the scene's device copy, which the Scene
 keeps while its spheres and background do not change (a picking loop uploads
 once). They take numpy arrays and stage them through torch tensors.
@@ -80,6 +83,17 @@ class AmbientLight:  # ray/objects.go:64-66
     ColorA: ColorF = (0.0, 0.0, 0.0)
     ColorB: ColorF = (0.0, 0.0, 0.0)
 
+    def Hit(self, directions, device: int = 0) -> np.ndarray:  # ray/objects.go:68-73
+        """AmbientLight.Hit for n rays of the given (n, 3) directions: (n, 3) float64
+        colours (a zero direction gives NaN, as in Go). Needs no scene."""
+        d = np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+        torch, rays = _stage_rays(np.zeros_like(d), d, device)
+        n = rays.shape[0]
+        rgb = torch.empty((n, 3), dtype=torch.float64, device=rays.device)
+        _lib.background_hit_async(_background(self), rays.data_ptr(), n, rgb.data_ptr(), device,
+                                  torch.cuda.current_stream(rays.device).cuda_stream)
+        return rgb.cpu().numpy()
+
 
 def DefaultBackground() -> AmbientLight:  # ray/objects.go:106-110
     return AmbientLight((1.0, 1.0, 1.0), (0.4, 0.65, 1.0))
@@ -141,6 +155,57 @@ class Scene:  # ray/objects.go:32-35
                             ids_t.data_ptr() if ids_t is not None else None, seg.data_ptr(),
                             stream=torch.cuda.current_stream(rays.device).cuda_stream)
         return rgb.cpu().numpy(), seg.cpu().numpy().view(np.uint32)
+
+    def Scatter(self, origins, directions, hits, seed: int, ids=None, bounce: int = 0,
+                device: int = 0) -> np.ndarray:  # ray/materials.go:13-64
+        """hits[i].Mat.Scatter(ray i, hits[i]) for n rays: a _lib.SCATTER_DTYPE array
+        (scattered 0: absorbed or no hit, every other field zero). hits: a
+        _lib.HIT_DTYPE array of the same length, e.g. Scene.Hit's; point, normal,
+        front_face and index are read from it. ids and seed as for RayColor; the
+        draws are those of `bounce`."""
+        o = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+        h = np.ascontiguousarray(hits)
+        if h.dtype != _lib.HIT_DTYPE:
+            raise TypeError("hits must use tray_amd._lib.HIT_DTYPE")
+        h = h.reshape(-1)
+        if len(h) != len(o):
+            raise ValueError("hits must hold one record per ray")
+        ids_np = None
+        if ids is not None:
+            ids_np = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            if ids_np.size != 2 * len(o):
+                raise ValueError("ids must hold a (pixel, sample) pair per ray")
+        torch, rays = _stage_rays(o, directions, device)
+        n = rays.shape[0]
+        hits_t = torch.from_numpy(h.view(np.float64).reshape(n, _lib.HIT_DTYPE.itemsize // 8)).to(rays.device)
+        ids_t = torch.from_numpy(ids_np.view(np.int32)).to(rays.device) if ids_np is not None else None
+        out = torch.empty((n, _lib.SCATTER_DTYPE.itemsize // 8), dtype=torch.float64, device=rays.device)
+        dev = self._device_scene(device)
+        dev.scatter_async(rays.data_ptr(), hits_t.data_ptr(), n, int(seed), out.data_ptr(),
+                          ids_t.data_ptr() if ids_t is not None else None, int(bounce),
+                          stream=torch.cuda.current_stream(rays.device).cuda_stream)
+        return out.cpu().numpy().reshape(-1).view(_lib.SCATTER_DTYPE)
+
+    def Occluded(self, origins, directions, t_end=math.inf, device: int = 0) -> np.ndarray:
+        """Whether anything lies in (1e-6, t_end) along each of n rays: (n,) bool,
+        Scene.Hit(...)["index"] >= 0 at one byte per ray and with a traversal that
+        stops at the first root. t_end: a scalar, or an (n,) array of per-ray ends
+        (NaN or <= 1e-6: an empty interval, False)."""
+        o = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+        ends = None
+        if np.ndim(t_end) > 0:
+            ends = np.ascontiguousarray(t_end, dtype=np.float64).reshape(-1)
+            if len(ends) != len(o):
+                raise ValueError("t_end must be a scalar or hold one end per ray")
+        torch, rays = _stage_rays(o, directions, device)
+        n = rays.shape[0]
+        ends_t = torch.from_numpy(ends).to(rays.device) if ends is not None else None
+        out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+        dev = self._device_scene(device)
+        dev.occluded_async(rays.data_ptr(), n, out.data_ptr(), math.inf if ends is not None else float(t_end),
+                           ends_t.data_ptr() if ends_t is not None else None,
+                           stream=torch.cuda.current_stream(rays.device).cuda_stream)
+        return out.cpu().numpy().astype(bool)
 
     def to_array(self) -> np.ndarray:
         """Flatten to the C-ABI's tray_sphere array; unsupported objects raise
