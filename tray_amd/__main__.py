@@ -4,6 +4,7 @@ have no meaning here).
 
     python -m tray_amd [-width 1280] [-height 720] [-r 64] [-d 50] [-seed 2] [-save out.png]
     python -m tray_amd -ansi [-s 4] ...   # main.go's terminal view, non-interactive (-exit)
+    python -m tray_amd -aov PREFIX ...    # also the first-hit feature buffers (include/tray_aov.h)
 """
 from __future__ import annotations
 
@@ -11,7 +12,25 @@ import argparse
 import sys
 import time
 
-from . import png, ray, terminal
+import numpy as np
+
+from . import _lib, png, ray, terminal
+
+
+def _srgba(rgb: np.ndarray) -> np.ndarray:
+    """ColorF.ToSRGBA of an (H, W, 3) float64 image (the host encoder of include/tray.h)."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+    rgba = np.zeros(rgb.shape[:2] + (4,), dtype=np.uint8)
+    _lib.check(_lib.lib().tray_to_srgba(rgb.ctypes.data, rgb.shape[0] * rgb.shape[1], rgba.ctypes.data))
+    return rgba
+
+
+def save_aov(prefix: str, aov: dict) -> None:
+    """PREFIX.npz with the five arrays of Tracer.RenderAOV, and the two guide images a
+    denoiser takes as PNGs: the albedo, and the normal mapped to colours by 0.5 n + 0.5."""
+    np.savez(prefix + ".npz", **aov)
+    png.save_png(prefix + "_albedo.png", _srgba(aov["albedo"]))
+    png.save_png(prefix + "_normal.png", _srgba(0.5 * aov["normal"] + 0.5))
 
 
 def main(argv=None) -> int:
@@ -22,6 +41,8 @@ def main(argv=None) -> int:
     ap.add_argument("-d", type=int, default=50, help="max depth")
     ap.add_argument("-seed", type=int, default=2)
     ap.add_argument("-save", default="out.png", help="output PNG ('' to skip)")
+    ap.add_argument("-aov", default="", metavar="PREFIX",
+                    help="also write the first-hit feature buffers: PREFIX.npz, PREFIX_albedo.png, PREFIX_normal.png")
     ap.add_argument("-ansi", action="store_true",
                     help="render at -s x the terminal size and draw it in the terminal (main.go:86-131)")
     ap.add_argument("-s", type=float, default=4, help="supersampling factor of -ansi")
@@ -39,6 +60,8 @@ def main(argv=None) -> int:
           f"{a.width * a.height * a.r / dt / 1e6:.1f} Mrays/s end to end", file=sys.stderr)
     if a.save:
         png.save_png(a.save, img)
+    if a.aov:
+        save_aov(a.aov, t.RenderAOV(scene))
     if a.ansi:
         cols, rows = terminal.terminal_size()
         print(terminal.ansi_halfblocks(terminal.scale_image(img, cols, rows * 2, a.s)))

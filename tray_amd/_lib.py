@@ -206,6 +206,25 @@ class Scatter(ctypes.Structure):
 
 assert ctypes.sizeof(Scatter) == 80 and Scatter.scattered.offset == 72
 
+# Every symbol include/tray_aov.h declares (the first-hit feature buffers; in none of the
+# three lists above).
+AOV_EXPORTS = (
+    "tray_aov_version",
+    "tray_render_aov_async",
+)
+
+# The buffers of tray_aov_buffers in declaration order: (name, channels, numpy dtype).
+AOV_BUFFERS = (("albedo", 3, np.float64), ("normal", 3, np.float64), ("depth", 1, np.float64),
+               ("coverage", 1, np.float64), ("index", 1, np.int32))
+
+
+class AovBuffers(ctypes.Structure):
+    """tray_aov_buffers: device pointers, each nullable."""
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in AOV_BUFFERS]
+
+
+assert ctypes.sizeof(AovBuffers) == 40
+
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
 DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear")
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
@@ -296,6 +315,10 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.tray_scatter_async.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64, vp, vp]
         L.tray_background_hit_async.argtypes = [ctypes.POINTER(Background), vp, ctypes.c_int64, vp, i32, vp]
         L.tray_scene_occluded_async.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_double, i32, vp, vp]
+    if hasattr(L, "tray_aov_version"):  # include/tray_aov.h; absent from older builds (A/B tools)
+        L.tray_aov_version.restype = i32
+        L.tray_render_aov_async.argtypes = [vp, ctypes.POINTER(CameraState), ctypes.POINTER(Params),
+                                            ctypes.POINTER(AovBuffers), vp]
     if hasattr(L, "tray_debug_set"):  # absent from older builds (A/B tools)
         L.tray_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
         L.tray_debug_clear.argtypes = [ctypes.c_char_p]
@@ -595,6 +618,18 @@ class DeviceScene:
         end = t_ends_ptr[i] (n x f64) when given, else t_end."""
         rc = self.L.tray_scene_occluded_async(self.handle, rays_ptr, t_ends_ptr, int(n), float(t_end), int(flags),
                                               out_ptr, stream)
+        if rc != TRAY_OK:
+            raise TrayError(rc, self.L.tray_last_error().decode())
+
+    def render_aov_async(self, camera: CameraState, params: Params, albedo_ptr: int | None = None,
+                         normal_ptr: int | None = None, depth_ptr: int | None = None,
+                         coverage_ptr: int | None = None, index_ptr: int | None = None,
+                         stream: int | None = None) -> None:
+        """tray_render_aov_async: the first-hit feature buffers of params' row set into device
+        buffers (rows x width x 3 f64, x 3 f64, f64, f64, i32); a None buffer is not written."""
+        out = AovBuffers(albedo_ptr, normal_ptr, depth_ptr, coverage_ptr, index_ptr)
+        rc = self.L.tray_render_aov_async(self.handle, ctypes.byref(camera), ctypes.byref(params), ctypes.byref(out),
+                                          stream)
         if rc != TRAY_OK:
             raise TrayError(rc, self.L.tray_last_error().decode())
 

@@ -1015,6 +1015,46 @@ int tray_scene_occluded_async(tray_scene_t sc, const tray_ray* rays_device, cons
     return TRAY_OK;
 }
 
+// ---- first-hit feature buffers (include/tray_aov.h) -----------------------------
+int32_t tray_aov_version(void) { return TRAY_AOV_VERSION; }
+
+int tray_render_aov_async(tray_scene_t sc, const tray_camera* cam, const tray_params* p, const tray_aov_buffers* out,
+                          void* stream) {
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
+    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null feature buffers (out)");
+    int rc = validate_params(p);
+    if (rc) return rc;
+    if (!out->albedo && !out->normal && !out->depth && !out->coverage && !out->index)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "every feature buffer is null: nothing to write");
+    const int64_t rows = tray_params_rows(p);
+    if (rows * (int64_t)p->width > kQueryMaxRays)
+        return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one feature-buffer call");
+    if (rows == 0) return TRAY_OK;
+    // One lane per pixel and a loop over its samples: rows x width x rays_per_pixel has no
+    // limit here (the megakernel's 8-row band limit, band_fits, is about its item indices).
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    k.width = p->width;
+    k.height = p->height;
+    k.spp = p->rays_per_pixel;
+    k.y_start = p->y_start;
+    k.rows = (int32_t)rows;
+    k.tile_rows = p->tile_rows;
+    k.tile_count = p->tile_rows > 0 ? p->tile_count : 1;
+    k.tile_index = p->tile_rows > 0 ? p->tile_index : 0;
+    k.ray_radius = p->ray_radius;
+    k.passes = 1;
+    k.pass0 = (uint32_t)p->pass;
+    camera_params(cam, k);
+    key_params(p->seed, k);
+    TRAY_HIP(hipSetDevice(sc->device));
+    TRAY_HIP(launch_render_aov(k, sc->has_bvh && !(p->flags & TRAY_FLAG_LINEAR_SCAN), sc->bvh_bound, *out,
+                               static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
 static hipError_t grow(void** buf, size_t* have, size_t bytes) {
     if (*have >= bytes) return hipSuccess;
     if (*buf) (void)hipFree(*buf);

@@ -3,7 +3,9 @@
 // (ray/objects.go:37-46, Sphere.Hit :81-104) and Scene.RayColor
 // (ray/objects.go:49-62) as kernels of their own, one ray (sample, path) per
 // lane; and (include/tray_shade.h) Material.Scatter (ray/materials.go:13-64),
-// AmbientLight.Hit (ray/objects.go:68-73) and the occlusion query, the same way.
+// AmbientLight.Hit (ray/objects.go:68-73) and the occlusion query, the same way;
+// and (include/tray_aov.h) the first-hit feature buffers of a frame, one pixel per
+// lane (aov_kernel).
 //
 // The arithmetic is the megakernel's, not a restatement of it: this file
 // includes tray_kernel.hip's device functions (get_ray, camera_block, draw,
@@ -384,6 +386,85 @@ __global__ __launch_bounds__(kQueryBlock) void scene_occluded_kernel(KernelParam
     static_cast<uint8_t*>(q.out)[i] = query_occluded(sv, S, q, org, dir, t_end) ? 1 : 0;
 }
 
+// First-hit feature buffers (include/tray_aov.h): one pixel per lane and a loop over the
+// pixel's samples; a wave is an 8x8 tile of pixels (of compact rows), a workgroup four
+// tiles. The lanes of a wave trace one small patch of the image, so their traversals stay
+// together (measured on C2 against a wave per 64-pixel row strip: 8 % faster, DESIGN.md
+// 8h), every lane of a launch runs the same trip count, and the sums are the contract's by
+// construction: sequential from zero in sample order, then one multiplication by 1 / r
+// (ray/tracer.go:132-145). Each sample is camera_rays_kernel's ray
+// (get_ray on the sample's camera block) and scene_hit_kernel's record (query_hit with
+// t_end = +inf, then the same normal), reduced in registers: nothing per sample is stored.
+// A miss adds +0 to the normal and depth sums, which changes no sum (none can be -0: they
+// start at +0).
+struct AovArgs {
+    tray_aov_buffers out;
+    double inv_spp;     // RN(1 / r), the host's quotient
+    uint32_t tiles_x;   // 8x8 pixel tiles per row of tiles: ceil(width / 8)
+    uint32_t samples;   // r, or 1 when only `index` is asked for (sample 0 decides it)
+};
+
+__global__ __launch_bounds__(kQueryBlock) void aov_kernel(KernelParams p, QueryArgs q, AovArgs a) {
+    const uint32_t tile = blockIdx.x * (kQueryBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t width = (uint32_t)p.width;
+    const uint32_t x = (tile % a.tiles_x) * 8u + (lane & 7u), j = (tile / a.tiles_x) * 8u + (lane >> 3);
+    if (x >= width || j >= (uint32_t)p.rows) return;  // the frame's right and lower edge, and tiles past the last
+    const uint32_t i = j * width + x;                 // < rows x width <= 2^31 - 1
+    const SceneView sv = scene_view(p);
+    const QStack S = lane_stack();
+    const int32_t y = row_of(p, (int32_t)j);
+    const uint32_t pixel = (uint32_t)y * width + x;   // global index: the draw block's pixel word
+    const uint32_t sample0 = p.pass0 * (uint32_t)p.spp;  // the draw block's sample word of s = 0
+    const double px = (double)x, py = (double)y;
+    D3 albedo = d3(0, 0, 0), normal = d3(0, 0, 0);
+    double depth = 0.0;
+    uint32_t hits = 0;
+    int32_t first = -1;
+    for (uint32_t s = 0; s < a.samples; ++s) {
+        // The camera, draw key and background are read from the kernel arguments where they
+        // are used (KernelParams is the first argument), as the megakernel reads them: held
+        // in scalar registers across the traversal they spill (71 spills without this).
+        const KernelParams& pk = kp_fresh();
+        D3 org, dir;
+        get_ray(pk, camera_block(pk, pixel, sample0 + s), px, py, org, dir);
+        const QHit h = query_hit(sv, S, q, org, dir, __builtin_inf());
+        D3 as, ns = d3(0, 0, 0);
+        double ds = 0.0;
+        if (h.ref < 0) {  // AmbientLight.Hit (ray/objects.go:68-73), as background_hit_kernel
+            const KernelParams& pb = kp_fresh();
+            const D3 bg_a = d3(pb.bg_a.x, pb.bg_a.y, pb.bg_a.z), bg_b = d3(pb.bg_b.x, pb.bg_b.y, pb.bg_b.z);
+            const D3 ud = unit_lsq(dir, h.a);
+            const double t = 0.5 * (ud.y + 1.0);
+            as = add(smul(bg_a, 1.0 - t), smul(bg_b, t));
+        } else {  // Sphere.Hit's record (ray/objects.go:98-102), as scene_hit_kernel
+            const double4 g = h.tree ? sv.bgeo[h.ref] : sv.geo[h.ref];
+            const MatRec* m = h.tree ? sv.bmat + h.ref : p.mat + h.ref;
+            const bool dielectric = m->type == kDielectric;  // attenuation (1,1,1), ray/materials.go:45
+            as = d3(dielectric ? 1.0 : m->albedo[0], dielectric ? 1.0 : m->albedo[1], dielectric ? 1.0 : m->albedo[2]);
+            const D3 point = add(org, smul(dir, h.t));
+            const D3 outward = sdiv_rcp(sub(point, d3(g.x, g.y, g.z)), m->radius, m->rinv);
+            ns = neg_if(outward, !(dot(dir, outward) < 0));
+            ds = h.t * sqrt_cr(h.a);  // t * Length(dir): h.a is LengthSquared's bits
+            ++hits;
+            if (s == 0) first = h.tree ? sv.bidx[h.ref] : h.ref;
+        }
+        albedo = add(albedo, as);
+        normal = add(normal, ns);
+        depth = depth + ds;
+    }
+    if (a.out.albedo) {
+        double* o = a.out.albedo + (size_t)i * 3;
+        o[0] = albedo.x * a.inv_spp, o[1] = albedo.y * a.inv_spp, o[2] = albedo.z * a.inv_spp;
+    }
+    if (a.out.normal) {
+        double* o = a.out.normal + (size_t)i * 3;
+        o[0] = normal.x * a.inv_spp, o[1] = normal.y * a.inv_spp, o[2] = normal.z * a.inv_spp;
+    }
+    if (a.out.depth) a.out.depth[i] = hits ? depth / (double)hits : 0.0;
+    if (a.out.coverage) a.out.coverage[i] = (double)hits * a.inv_spp;
+    if (a.out.index) a.out.index[i] = first;
+}
+
 // The stacks of one workgroup; the dynamic-LDS default limit (64 KB) bounds them.
 static size_t query_stack_bytes(int32_t stack_cap) { return (size_t)stack_cap * kQueryBlock * sizeof(uint32_t); }
 constexpr size_t kQueryLdsMax = 64 * 1024;
@@ -459,6 +540,25 @@ hipError_t launch_scene_occluded(const KernelParams& p, bool use_bvh, double bou
     q.t_end = t_end;
     hipLaunchKernelGGL(scene_occluded_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), lds,
                        stream, p, q, t_ends);
+    return hipGetLastError();
+}
+
+hipError_t launch_render_aov(KernelParams p, bool use_bvh, double bound, const tray_aov_buffers& out,
+                             hipStream_t stream) {
+    const uint32_t n = (uint32_t)p.rows * (uint32_t)p.width;
+    if (n == 0) return hipSuccess;
+    p.div_tile_rows = make_fastdiv((uint32_t)std::max(p.tile_rows, 1));  // row_of
+    size_t lds = 0;
+    const QueryArgs q = query_args(p, use_bvh, bound, nullptr, n, lds);
+    AovArgs a{};
+    a.out = out;
+    a.inv_spp = 1.0 / (double)p.spp;
+    a.tiles_x = ((uint32_t)p.width + 7u) / 8u;
+    a.samples = out.albedo || out.normal || out.depth || out.coverage ? (uint32_t)p.spp : 1u;
+    const uint32_t tiles = a.tiles_x * (((uint32_t)p.rows + 7u) / 8u);  // a wave each: <= 2^25 + 2^28
+    constexpr uint32_t kTilesPerBlock = kQueryBlock / 64;
+    hipLaunchKernelGGL(aov_kernel, dim3((tiles + kTilesPerBlock - 1u) / kTilesPerBlock), dim3(kQueryBlock), lds, stream,
+                       p, q, a);
     return hipGetLastError();
 }
 

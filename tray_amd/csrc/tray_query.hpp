@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/tray_aov.h"
 #include "../../include/tray_shade.h"  // includes tray_query.h
 #include "tray_kernel.hpp"
 
@@ -45,5 +46,12 @@ hipError_t launch_background_hit(V3 color_a, V3 color_b, const tray_ray* rays, u
 hipError_t launch_scene_occluded(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays,
                                  const double* t_ends, uint32_t n, double t_end, uint8_t* occluded,
                                  hipStream_t stream);
+
+// include/tray_aov.h.
+// The first-hit feature buffers of p's row set (p.rows x p.width pixels, p.spp samples
+// each, pass p.pass0): p's scene, camera, image, row-set and draw-key fields. use_bvh
+// and bound as for launch_scene_hit. Null buffers of `out` are not written.
+hipError_t launch_render_aov(KernelParams p, bool use_bvh, double bound, const tray_aov_buffers& out,
+                             hipStream_t stream);
 
 }  // namespace tray

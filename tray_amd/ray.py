@@ -19,6 +19,7 @@ against `ray.New(w, h)` / `(*Tracer).Render(scene)` reads the same here:
     Material.Scatter(r, rec)    materials.go:13 Scene.Scatter(origins, directions, hits, seed) -> SCATTER_DTYPE array
     AmbientLight.Hit(r)         objects.go:68   AmbientLight.Hit(directions) -> (n, 3) colours
     (no Go counterpart)                         Scene.Occluded(origins, directions, t_end) -> (n,) bool
+    (no Go counterpart)                         Tracer.RenderAOV(scene) -> albedo, normal, depth, coverage, index
 
 The last six are batched (include/tray_query.h, tray_shade.h): arrays of rays in, arrays of
 results out, each one kernel launch on the scene's device copy, which the Scene
@@ -439,6 +440,30 @@ class Tracer:  # ray/tracer.go:25-36
         self.Camera.Initialize(self.width, self.height)
         self._render_rows(0, self.height, scene)
         return self.imageData
+
+    def RenderAOV(self, scene: Scene | None, yStart: int = 0, yEnd: int | None = None, pass_: int = 0) -> dict:
+        """The first-hit feature buffers (include/tray_aov.h) of rows [yStart, yEnd) of the
+        frame Render(scene) draws, with Render's defaulting: a dict of numpy arrays, albedo
+        and normal (rows, W, 3) float64, depth and coverage (rows, W) float64, index
+        (rows, W) int32 (-1: sample 0 misses). One fused launch over the frame's own camera
+        rays of pass `pass_`; no Go counterpart. Set Seed for buffers that match a render."""
+        import torch
+
+        scene = self._apply_defaults(scene)
+        self.Camera.Initialize(self.width, self.height)
+        device = self.Devices[0] if self.Devices else self.Device
+        params = _lib.make_params(self.width, self.height, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius,
+                                  self._seed(), yStart, self.height if yEnd is None else yEnd, pass_=pass_)
+        rows = _lib.params_rows(params)
+        where = torch.device(f"cuda:{int(device)}")
+        bufs = {name: torch.empty((rows, self.width, ch)[: 3 if ch > 1 else 2],
+                                  dtype=torch.float64 if dt is np.float64 else torch.int32, device=where)
+                for name, ch, dt in _lib.AOV_BUFFERS}
+        if rows > 0:  # an empty row set has no buffers to point at
+            scene._device_scene(device).render_aov_async(
+                self.Camera._state, params, *(bufs[name].data_ptr() for name, _, _ in _lib.AOV_BUFFERS),
+                stream=torch.cuda.current_stream(where).cuda_stream)
+        return {name: t.cpu().numpy() for name, t in bufs.items()}
 
     def RenderLines(self, idx: int, yStart: int, yEnd: int, scene: Scene) -> None:  # ray/tracer.go:120-155
         """Render rows [yStart, yEnd) with the current (initialized) camera and
