@@ -99,13 +99,19 @@ def go_tan(x):
     return -y if sign else y
 
 
-def camera_initialize(position, look_at, up, vfov, focal, width, height):
+def camera_initialize(position, look_at, up, vfov, focal, width, height, focus=None, aperture=0.0):
+    """Camera.Initialize (camera.go:43-105) for a setup that needs none of its defaults but
+    FocusDistance == 0 -> FocalLength (focus=None). aperture > 0 adds the lens disc."""
     f64 = np.float64
     position = tuple(f64(c) for c in position)
     view = sub(position, tuple(f64(c) for c in look_at))
     w = unit(view)
     u = unit(cross(tuple(f64(c) for c in up), w))
     v = cross(w, u)
+    zero = (f64(0), f64(0), f64(0))
+    defocus_radius = f64(aperture) / f64(2.0)
+    du = smul(u, defocus_radius) if aperture != 0 else zero  # Go's SMul(u, 0) holds -0 where u < 0; never read
+    dv = smul(v, defocus_radius) if aperture != 0 else zero
     theta = f64(vfov) * f64(float.fromhex("0x1.1df46a2529d39p-6"))  # math.Pi/180, folded exactly by Go
     viewport_h = f64(2.0) * f64(focal) * f64(go_tan(float(theta / f64(2.0))))
     viewport_w = (f64(width) / f64(height)) * viewport_h
@@ -116,9 +122,28 @@ def camera_initialize(position, look_at, up, vfov, focal, width, height):
     py = (vertical[0] / f64(height), vertical[1] / f64(height), vertical[2] / f64(height))
     upper_left = sub(position, add(add(smul(w, f64(focal)), smul(horizontal, f64(0.5))), smul(vertical, f64(0.5))))
     p00 = add(upper_left, smul(add(px, py), f64(0.5)))
-    zero = (f64(0), f64(0), f64(0))
     # tray_camera layout: position, pixel00, pixel_x, pixel_y, defocus_u, defocus_v, aperture, focus, focal
-    return np.array([*position, *p00, *px, *py, *zero, *zero, 0.0, float(focal), float(focal)])
+    return np.array([*position, *p00, *px, *py, *du, *dv, float(aperture),
+                     float(focal if focus is None or focus == 0 else focus), float(focal)])
+
+
+def get_ray(cam, x, y, ox, oy, lens=(0.0, 0.0)):
+    """Camera.GetRay (camera.go:113-142) for pixel (x, y) with the sub-pixel offset (ox, oy);
+    `lens` is the unit-disc draw rng.InDisc(1.0) of camera.go:128 (read only when Aperture > 0).
+    Returns (origin, direction) as tuples of components."""
+    f64 = np.float64
+    pos, p00, pxv, pyv = (tuple(f64(c) for c in cam[i:i + 3]) for i in (0, 3, 6, 9))
+    sample = add(add(p00, smul(pxv, x + ox)), smul(pyv, y + oy))  # pixel00.Plus(a, b) = AddMultiple
+    origin = pos
+    direction = sub(sample, pos)
+    if cam[18] > 0:
+        du, dv = tuple(f64(c) for c in cam[12:15]), tuple(f64(c) for c in cam[15:18])
+        offset = add(smul(du, lens[0]), smul(dv, lens[1]))
+        focus_time = f64(cam[19]) / f64(cam[20])
+        focus_point = add(pos, smul(direction, focus_time))
+        origin = add(pos, offset)
+        direction = sub(focus_point, origin)
+    return origin, direction
 
 
 # ---------------------------------------------------- objects.go, vectorised --

@@ -38,6 +38,25 @@ def beam(cam, spp, ray_radius, xa, xb, ya, yb):
     return pos, b0 - pos, ra, rb
 
 
+def beam_normal(v):
+    """tray_kernel.hip beam_normal: comfortably inside binary64's normal range (a NaN is not)."""
+    return bool(v >= 1e-250 and v <= 1e250)
+
+
+def beam_ok(cam, spp, ray_radius, xa, xb, ya, yb):
+    """pixel_beam's `ok`: false means the pixel gets no list and its camera rays traverse.
+    The axis must be longer than twice the disc radii, and |D|^2 and the two pixel
+    vectors' squares must be comfortably normal (reaches() divides by the first and a far
+    radius built from a square that underflowed is zero)."""
+    _, D, ra, rb = beam(cam, spp, ray_radius, xa, xb, ya, yb)
+    pxv = np.array(cam.pixel_x[:]); pyv = np.array(cam.pixel_y[:])
+    with np.errstate(all="ignore"):
+        dn2 = D[0] * D[0] + D[1] * D[1] + D[2] * D[2]
+        lx2 = pxv[0] * pxv[0] + pxv[1] * pxv[1] + pxv[2] * pxv[2]
+        ly2 = pyv[0] * pyv[0] + pyv[1] * pyv[1] + pyv[2] * pyv[2]
+        return bool(np.sqrt(dn2) > 2.0 * (ra + rb)) and beam_normal(dn2) and beam_normal(lx2) and beam_normal(ly2)
+
+
 def reaches(pos, D, ra, rb, centers, radii):
     """beam_reaches for every sphere (vectorised)."""
     dn2 = D @ D

@@ -35,6 +35,34 @@
 // outside the range have no tree (build_bvh returns false) and take the
 // linear scan, which is the reference's own loop.
 //
+// Range of the direction: the argument above also needs a direction FP32 can
+// carry. trav_begin32 replaces a component with |d_k| < 1e-30 by +1e-30, which
+// drops its sign. That is harmless while the direction as a whole is not small:
+// with a = |d|^2 >= 1e-30 some component has |d_j| >= 1e-15 / sqrt(3), a box is
+// reached at |t| <= 2 sqrt(3) M / |d_j| < 6.1e15 M, and over that span a clamped
+// component moves the ray by less than 6.1e15 M * 1e-30 (the true one by no
+// more): 1e-14 M against a padding of 4e-6 M. On such an axis the ray stays
+// where its origin is, inside the padded slab of any box it can hit, whose two
+// plane distances -+4e-6 M * 1e30 then lie far outside every t in play and
+// constrain nothing. Below a = 1e-30 nothing of this holds: at |d| <= 1e-30
+// every component is replaced, the ray is taken to run towards (+, +, +), and
+// boxes on its real path are culled (a pinhole camera whose FocalLength is
+// 2^-100 has such rays: Go sets a camera ray's length freely, and Sphere.Hit
+// does not care). At the other end a <= 1e30 keeps every |d_k| <= 1e15, so
+// 1 / d_k >= 1e-15 and the smallest product that matters, padding * inv >=
+// 4e-6 * 1e-15, stays far above FLT_MIN: no underflow, the relative-error
+// argument stands. (A direction longer than about 1e15 cannot hit a tree sphere
+// anyway: t > Interval.Start = 1e-6 puts the hit beyond 1e9 > 2 * 2^28.) A NaN or
+// infinite component fails both tests. So the slab test is used for
+// 1e-30 <= |d|^2 <= 1e30 only (slab_dir_ok, tray_kernel.hip), and every ray
+// outside it takes a path with no FP32 in it: the ray queries scan the list
+// (query_hit), and the megakernel tests such a camera ray against every tree
+// sphere in FP64 where it would otherwise read its candidate list (the refill;
+// under the any-order rule that is the list scan). Scattered rays are of order
+// one: Metal and Dielectric scatter from Unit(direction), Lambertian from a unit
+// normal plus a unit vector with NearZero replaced. The candidate lists have
+// their own range test (pixel_beam's ok, tray_kernel.hip).
+//
 // Build: binned SAH over sphere centroids into a binary tree (object-median
 // splits once a branch gets deep, so depth stays bounded), then collapsed into
 // 4-wide nodes by repeatedly opening the largest-area inner child. Spheres

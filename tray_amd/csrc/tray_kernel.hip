@@ -520,6 +520,16 @@ __device__ __forceinline__ void trav_globals(Trav& T, const SceneView& sv, const
         if (g < sv.n_global) test_slot(T, sv, sv.global_first + g, org, dir);
 }
 
+// The direction lengths the FP32 slab test is conservative for (tray_bvh.cpp, "Range of
+// the direction"): 1e-30 <= |dir|^2 <= 1e30; a NaN fails. Go sets a camera ray's length
+// freely (pinhole: proportional to FocalLength; lens: about FocusDistance), and a
+// caller's ray has any length. Whoever calls trav_begin32 answers for the range: the ray
+// queries send any other ray through the linear scan (query_hit), the megakernel tests
+// every tree sphere for such a camera ray (the refill), and the begin step's rays are
+// scattered ones, of order one (Metal and Dielectric start from Unit(direction),
+// Lambertian from a unit normal plus a unit vector with NearZero replaced).
+__device__ __forceinline__ bool slab_dir_ok(double a) { return a >= 1e-30 && a <= 1e30; }
+
 // The FP32 traversal setup of a segment whose FP64 part (trav_globals) is done.
 __device__ __forceinline__ void trav_begin32(Trav& T, const SceneView& sv, const D3& org, const D3& dir) {
     T.cur = sv.n_nodes > 0 ? 0u : kBvhNone;  // the root
@@ -1603,18 +1613,24 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                     trav_globals(T, sv, L.org, L.dir);
                     if constexpr (kStats) st.spheres += (uint64_t)sv.n_global;
                     const uint32_t n_cand = cand.w >> 16;
-                    if (n_cand <= kCandSlots) {
+                    // A camera ray's direction has whatever length Go's camera gives it
+                    // (slab_dir_ok): outside the FP32 slab test's range the ray tests every
+                    // tree sphere in FP64 here, as if all of them were its candidates.
+                    const bool listed = n_cand <= kCandSlots;
+                    if (listed || !slab_dir_ok(T.a)) {
                         // Scene.Hit of a camera ray: the out-of-tree spheres and the pixel's
                         // candidates under the any-order rule (every other tree sphere is out
                         // of the ray's reach), no traversal.
                         uint64_t lo = ((uint64_t)cand.y << 32) | cand.x, hi = ((uint64_t)cand.w << 32) | cand.z;
+                        // the tree spheres are the first slots
+                        const uint32_t n_test = listed ? n_cand : (uint32_t)sv.global_first;
 #pragma unroll 1
-                        for (uint32_t k = 0; k < n_cand; ++k) {
-                            test_slot(T, sv, (int32_t)(lo & 0xFFFFu), L.org, L.dir);
+                        for (uint32_t k = 0; k < n_test; ++k) {
+                            test_slot(T, sv, listed ? (int32_t)(lo & 0xFFFFu) : (int32_t)k, L.org, L.dir);
                             lo = (lo >> 16) | (hi << 48);
                             hi >>= 16;
                         }
-                        if constexpr (kStats) st.spheres += n_cand;
+                        if constexpr (kStats) st.spheres += n_test;
                         T.cur = kBvhNone;  // traversal done: the lane waits for the shade phase
                         cam_hit = true;
                     } else {
@@ -2115,8 +2131,20 @@ __device__ __forceinline__ bool beam_reaches(const D3& pos, const D3& D, double 
 struct Beam {
     D3 pos, D;
     double dn2, dn, ra, rb, scale;
-    bool ok;  // false: degenerate (the axis is not longer than twice the disc radii)
+    // false: no list, the pixel's camera rays traverse. Either the beam is degenerate
+    // (the axis is not longer than twice the disc radii) or one of |D|^2, |pixel_x|^2,
+    // |pixel_y|^2 is not comfortably normal (beam_normal; a NaN is not). beam_reaches
+    // divides by dn2 and scales the far radius by tc ~ |C - pos| / |D|: a dn2 near the
+    // subnormals keeps a few bits (Go's FocalLength is free: 2^-530 squares to one), and
+    // tc and d_perp are then noise. A pixel vector whose square underflows makes the far
+    // radius zero, which a lens camera's focus time (FocusDistance / FocalLength, as
+    // free) would have scaled back to size. With the three in range every product
+    // above is normal. The lens vectors need no test: ra is not scaled by the focus
+    // time, so an |ra| whose square underflows (below 2^-511) adds at most
+    // tc * 2^-510 <= 2^30 / 1e-125 * 2^-510 < 1e-19 to a reach whose margin is >= 1e-6.
+    bool ok;
 };
+__device__ __forceinline__ bool beam_normal(double v) { return v >= 1e-250 && v <= 1e250; }
 __device__ __forceinline__ Beam pixel_beam(const KernelParams& p, double xa, double xb, double ya, double yb) {
     Beam b;
     b.pos = d3(p.cam.position[0], p.cam.position[1], p.cam.position[2]);
@@ -2128,7 +2156,8 @@ __device__ __forceinline__ Beam pixel_beam(const KernelParams& p, double xa, dou
     const bool lens = p.cam.aperture > 0;
     const D3 s0 = add(add(p00, smul(pxv, 0.5 * (xa + xb))), smul(pyv, 0.5 * (ya + yb)));
     const D3 b0 = lens ? add(b.pos, smul(sub(s0, b.pos), p.focus_time)) : s0;
-    const double lx = __builtin_sqrt(length_sq(pxv)), ly = __builtin_sqrt(length_sq(pyv));
+    const double lx2 = length_sq(pxv), ly2 = length_sq(pyv);
+    const double lx = __builtin_sqrt(lx2), ly = __builtin_sqrt(ly2);
     // |RayRadius|: Go's RenderLines accepts a negative radius and InDisc(r) is
     // symmetric (disc() scales by the signed r), so the disc's extent is |r|.
     const double aa = (p.spp > 1 ? __builtin_fabs(p.ray_radius) * __builtin_sqrt(lx * lx + ly * ly) : 0.0) +
@@ -2138,7 +2167,7 @@ __device__ __forceinline__ Beam pixel_beam(const KernelParams& p, double xa, dou
     b.D = sub(b0, b.pos);
     b.dn2 = length_sq(b.D);
     b.dn = __builtin_sqrt(b.dn2);
-    b.ok = b.dn > 2.0 * (b.ra + b.rb) && b.dn2 > 0;
+    b.ok = b.dn > 2.0 * (b.ra + b.rb) && beam_normal(b.dn2) && beam_normal(lx2) && beam_normal(ly2);
     b.scale = 1.0 + __builtin_fmax(__builtin_fmax(__builtin_fabs(b.pos.x), __builtin_fabs(b.pos.y)), __builtin_fabs(b.pos.z));
     return b;
 }

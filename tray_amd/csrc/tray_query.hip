@@ -79,7 +79,8 @@ struct QHit {
 
 // Per ray: the BVH when the launch has one, the origin lies inside the bound its
 // padding proof needs, and the direction is finite and of a length FP32 can carry
-// (trav_begin32 clamps components below 1e-30); any other ray takes the
+// (slab_dir_ok, tray_kernel.hip: the one range this choice and the megakernel's camera
+// rays share); any other ray takes the
 // reference-order linear scan, which has no such conditions. Both give
 // min over spheres of (t_i, i) with t_i in (1e-6, t_end) (the any-order rule,
 // tray_kernel.hip): the traversal by starting its culling distance at t_end,
@@ -93,7 +94,7 @@ __device__ __forceinline__ QHit query_hit(const SceneView& sv, const QStack& S, 
     h.ref = -1;
     const double M = q.bound;
     const bool inside = __builtin_fabs(org.x) <= M && __builtin_fabs(org.y) <= M && __builtin_fabs(org.z) <= M;
-    h.tree = q.use_bvh != 0 && inside && h.a >= 1e-30 && h.a <= 1e30;
+    h.tree = q.use_bvh != 0 && inside && slab_dir_ok(h.a);
     if (!(t_end > 1e-6)) return h;  // an empty interval surrounds no root
     if (h.tree) {
         Trav T;
@@ -135,7 +136,7 @@ __device__ __forceinline__ bool query_occluded(const SceneView& sv, const QStack
     const double a = length_sq(dir);
     const double M = q.bound;
     const bool inside = __builtin_fabs(org.x) <= M && __builtin_fabs(org.y) <= M && __builtin_fabs(org.z) <= M;
-    const bool tree = q.use_bvh != 0 && inside && a >= 1e-30 && a <= 1e30;
+    const bool tree = q.use_bvh != 0 && inside && slab_dir_ok(a);
     if (!(t_end > 1e-6)) return false;  // an empty interval (a NaN end included) surrounds no root
     if (tree) {
         Trav T;
