@@ -5,6 +5,7 @@ have no meaning here).
     python -m tray_amd [-width 1280] [-height 720] [-r 64] [-d 50] [-seed 2] [-save out.png]
     python -m tray_amd -ansi [-s 4] ...   # main.go's terminal view, non-interactive (-exit)
     python -m tray_amd -aov PREFIX ...    # also the first-hit feature buffers (include/tray_aov.h)
+    python -m tray_amd -denoise -r 16 ... # the frame filtered on the device (include/tray_denoise.h)
 """
 from __future__ import annotations
 
@@ -43,6 +44,9 @@ def main(argv=None) -> int:
     ap.add_argument("-save", default="out.png", help="output PNG ('' to skip)")
     ap.add_argument("-aov", default="", metavar="PREFIX",
                     help="also write the first-hit feature buffers: PREFIX.npz, PREFIX_albedo.png, PREFIX_normal.png")
+    ap.add_argument("-denoise", action="store_true",
+                    help="save the frame after the guided a-trous filter (include/tray_denoise.h); "
+                         "with -aov also PREFIX_denoised.png")
     ap.add_argument("-ansi", action="store_true",
                     help="render at -s x the terminal size and draw it in the terminal (main.go:86-131)")
     ap.add_argument("-s", type=float, default=4, help="supersampling factor of -ansi")
@@ -54,14 +58,17 @@ def main(argv=None) -> int:
     t.NumRaysPerPixel, t.MaxDepth, t.Seed = a.r, a.d, a.seed
     scene = ray.RichScene(a.seed)
     t0 = time.perf_counter()
-    img = t.Render(scene)
+    img = t.RenderDenoised(scene) if a.denoise else t.Render(scene)
     dt = time.perf_counter() - t0
-    print(f"rendered {a.width}x{a.height} r={a.r} d={a.d} ({len(scene.Objects)} objects) in {dt:.3f} s: "
+    print(f"rendered {a.width}x{a.height} r={a.r} d={a.d}{' denoised' if a.denoise else ''} "
+          f"({len(scene.Objects)} objects) in {dt:.3f} s: "
           f"{a.width * a.height * a.r / dt / 1e6:.1f} Mrays/s end to end", file=sys.stderr)
     if a.save:
         png.save_png(a.save, img)
     if a.aov:
         save_aov(a.aov, t.RenderAOV(scene))
+        if a.denoise:
+            png.save_png(a.aov + "_denoised.png", img)
     if a.ansi:
         cols, rows = terminal.terminal_size()
         print(terminal.ansi_halfblocks(terminal.scale_image(img, cols, rows * 2, a.s)))

@@ -225,6 +225,31 @@ class AovBuffers(ctypes.Structure):
 
 assert ctypes.sizeof(AovBuffers) == 40
 
+# Every symbol include/tray_denoise.h declares (the a-trous denoiser guided by the feature
+# buffers; in none of the four lists above).
+DENOISE_EXPORTS = (
+    "tray_denoise_version",
+    "tray_denoise_default_params",
+    "tray_denoise_workspace_bytes",
+    "tray_denoise_async",
+)
+DENOISE_DEMODULATE = 1  # TRAY_DENOISE_DEMODULATE
+
+
+class DenoiseGuides(ctypes.Structure):
+    """tray_denoise_guides: device pointers, each nullable."""
+    _fields_ = [("albedo", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("depth", ctypes.c_void_p)]
+
+
+class DenoiseParams(ctypes.Structure):
+    """tray_denoise_params."""
+    _fields_ = [("width", ctypes.c_int32), ("rows", ctypes.c_int32), ("iterations", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("sigma_color", ctypes.c_double), ("sigma_normal", ctypes.c_double),
+                ("sigma_depth", ctypes.c_double)]
+
+
+assert ctypes.sizeof(DenoiseGuides) == 24 and ctypes.sizeof(DenoiseParams) == 40
+
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
 DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear")
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
@@ -319,6 +344,12 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.tray_aov_version.restype = i32
         L.tray_render_aov_async.argtypes = [vp, ctypes.POINTER(CameraState), ctypes.POINTER(Params),
                                             ctypes.POINTER(AovBuffers), vp]
+    if hasattr(L, "tray_denoise_version"):  # include/tray_denoise.h; absent from older builds (A/B tools)
+        L.tray_denoise_version.restype = i32
+        L.tray_denoise_default_params.argtypes = [i32, i32, ctypes.POINTER(DenoiseParams)]
+        L.tray_denoise_workspace_bytes.argtypes = [ctypes.POINTER(DenoiseParams), ctypes.POINTER(ctypes.c_size_t)]
+        L.tray_denoise_async.argtypes = [vp, ctypes.POINTER(DenoiseGuides), ctypes.POINTER(DenoiseParams), vp, vp,
+                                         ctypes.c_size_t, i32, vp]
     if hasattr(L, "tray_debug_set"):  # absent from older builds (A/B tools)
         L.tray_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
         L.tray_debug_clear.argtypes = [ctypes.c_char_p]
@@ -525,6 +556,42 @@ def release_cache(device: int = -1) -> None:
 def linear_to_srgba_async(rgb_ptr: int, n_pixels: int, rgba_ptr: int, device: int = 0, stream: int | None = None):
     """tray_linear_to_srgba_async: ColorF.ToSRGBA over device buffers (n x 3 f64 -> n x 4 u8)."""
     check(lib().tray_linear_to_srgba_async(rgb_ptr, n_pixels, rgba_ptr, device, stream))
+
+
+def denoise_params(width: int, rows: int, lib_path: str | None = None, **overrides) -> DenoiseParams:
+    """tray_denoise_default_params for a width x rows image, with fields overridden by name."""
+    p = DenoiseParams()
+    L = lib(lib_path)
+    if L.tray_denoise_default_params(int(width), int(rows), ctypes.byref(p)) != TRAY_OK:
+        raise TrayError(TRAY_ERR_INVALID_ARGUMENT, L.tray_last_error().decode())
+    for name, value in overrides.items():
+        if name not in dict(DenoiseParams._fields_):
+            raise ValueError(f"unknown denoise parameter {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def denoise_workspace_bytes(params: DenoiseParams, lib_path: str | None = None) -> int:
+    n = ctypes.c_size_t(0)
+    L = lib(lib_path)
+    rc = L.tray_denoise_workspace_bytes(ctypes.byref(params), ctypes.byref(n))
+    if rc != TRAY_OK:
+        raise TrayError(rc, L.tray_last_error().decode())
+    return int(n.value)
+
+
+def denoise_async(colour_ptr: int, params: DenoiseParams, out_ptr: int, workspace_ptr: int | None,
+                  workspace_bytes: int, albedo_ptr: int | None = None, normal_ptr: int | None = None,
+                  depth_ptr: int | None = None, device: int = 0, stream: int | None = None,
+                  lib_path: str | None = None) -> None:
+    """tray_denoise_async: the guided a-trous filter of include/tray_denoise.h over device buffers
+    (rows x width x 3 f64 in and out; a None guide drops its term). Only enqueues on `stream`."""
+    guides = DenoiseGuides(albedo_ptr, normal_ptr, depth_ptr)
+    L = lib(lib_path)
+    rc = L.tray_denoise_async(colour_ptr, ctypes.byref(guides), ctypes.byref(params), out_ptr, workspace_ptr,
+                              int(workspace_bytes), int(device), stream)
+    if rc != TRAY_OK:
+        raise TrayError(rc, L.tray_last_error().decode())
 
 
 def camera_rays_count(params: Params) -> int:

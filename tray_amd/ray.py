@@ -20,8 +20,10 @@ against `ray.New(w, h)` / `(*Tracer).Render(scene)` reads the same here:
     AmbientLight.Hit(r)         objects.go:68   AmbientLight.Hit(directions) -> (n, 3) colours
     (no Go counterpart)                         Scene.Occluded(origins, directions, t_end) -> (n,) bool
     (no Go counterpart)                         Tracer.RenderAOV(scene) -> albedo, normal, depth, coverage, index
+    (no Go counterpart)                         Tracer.Denoise(frame, aov) -> (H, W, 3) float64, the guided filter
+    (no Go counterpart)                         Tracer.RenderDenoised(scene) -> (H, W, 4) uint8 RGBA, filtered on the device
 
-The last six are batched (include/tray_query.h, tray_shade.h): arrays of rays in, arrays of
+The six from CameraRays to RenderAOV are batched (include/tray_query.h, tray_shade.h): arrays of rays in, arrays of
 results out, each one kernel launch on the scene's device copy, which the Scene
 keeps while its spheres and background do not change (a picking loop uploads
 once). They take numpy arrays and stage them through torch tensors.
@@ -464,6 +466,92 @@ class Tracer:  # ray/tracer.go:25-36
                 self.Camera._state, params, *(bufs[name].data_ptr() for name, _, _ in _lib.AOV_BUFFERS),
                 stream=torch.cuda.current_stream(where).cuda_stream)
         return {name: t.cpu().numpy() for name, t in bufs.items()}
+
+    def _denoise_device(self, torch, colour, aov: dict, overrides: dict):
+        """tray_denoise_async on device tensors: colour (rows, W, 3) float64 and the guides of
+        `aov` (albedo, normal, depth; a missing or None entry drops its term) -> a new
+        (rows, W, 3) float64 tensor, enqueued on the current stream."""
+        rows, width = int(colour.shape[0]), int(colour.shape[1])
+        params = _lib.denoise_params(width, rows, **overrides)
+        guides = {name: aov.get(name) for name in ("albedo", "normal", "depth")}
+        nbytes = _lib.denoise_workspace_bytes(params)
+        out = torch.empty_like(colour)
+        work = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=colour.device)
+        _lib.denoise_async(colour.data_ptr(), params, out.data_ptr(), work.data_ptr() if nbytes else None, nbytes,
+                           *(g.data_ptr() if g is not None else None for g in guides.values()),
+                           device=colour.device.index or 0,
+                           stream=torch.cuda.current_stream(colour.device).cuda_stream)
+        # `work` may be freed here: torch's allocator reuses it only for work on this same stream
+        return out
+
+    def Denoise(self, frame, aov: dict, yStart: int = 0, yEnd: int | None = None, tile_rows: int = 0,
+                **overrides) -> np.ndarray:
+        """The guided a-trous filter of include/tray_denoise.h over `frame`, a linear (rows, W, 3)
+        float64 image (Tracer.linear), with the feature buffers RenderAOV returned for the same
+        rows: (rows, W, 3) float64. overrides: fields of tray_denoise_params (iterations, flags,
+        sigma_color, sigma_normal, sigma_depth). No Go counterpart.
+
+        yStart, yEnd and tile_rows change nothing in the result: they exist only so that a caller
+        who rendered a row set can say which, and be refused where the filter cannot serve it. The
+        filter needs spatially contiguous rows, so [yStart, yEnd) must be a row range of the image
+        with exactly the frame's number of rows (else ValueError), and any tile_rows > 0, an
+        interleaved row set, raises ValueError."""
+        import torch
+
+        yEnd = self.height if yEnd is None else yEnd
+        if tile_rows > 0:
+            raise ValueError("Denoise needs spatially contiguous rows: interleaved row sets (tile_rows > 0) are not")
+        frame = np.ascontiguousarray(frame, dtype=np.float64)
+        if not 0 <= yStart <= yEnd <= self.height or frame.shape != (yEnd - yStart, self.width, 3):
+            raise ValueError(f"frame must hold rows [{yStart}, {yEnd}) of the {self.width}-wide image as "
+                             f"(rows, W, 3); got {frame.shape}")
+        host = {}
+        for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1)):
+            g = aov.get(name)
+            if g is None:
+                continue
+            g = np.ascontiguousarray(g, dtype=np.float64)
+            if g.shape != frame.shape[:2] + ((3,) if ch == 3 else ()):
+                raise ValueError(f"{name} must cover the frame's rows; got {g.shape}")
+            host[name] = g
+        where = torch.device(f"cuda:{int(self.Devices[0] if self.Devices else self.Device)}")
+        if frame.size == 0:
+            _lib.denoise_params(self.width, 0, **overrides)  # still refuses unknown fields
+            return frame.copy()
+        out = self._denoise_device(torch, torch.from_numpy(frame).to(where),
+                                   {n: torch.from_numpy(g).to(where) for n, g in host.items()}, overrides)
+        return out.cpu().numpy()
+
+    def RenderDenoised(self, scene: Scene | None, **overrides) -> np.ndarray:
+        """Render(scene) at the tracer's few rays per pixel, made presentable: a linear FP64
+        render (tray_render_async), the feature buffers of the same samples
+        (tray_render_aov_async), the guided filter (tray_denoise_async) and ColorF.ToSRGBA
+        (tray_linear_to_srgba_async), all enqueued on one stream with no host round trip in
+        between. Returns (H, W, 4) uint8 RGBA like Render and keeps it in imageData; `linear`
+        holds the denoised FP64 frame. overrides as for Denoise."""
+        import torch
+
+        scene = self._apply_defaults(scene)
+        self.Camera.Initialize(self.width, self.height)
+        device = int(self.Devices[0] if self.Devices else self.Device)
+        where = torch.device(f"cuda:{device}")
+        params = _lib.make_params(self.width, self.height, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius,
+                                  self._seed(), 0, self.height)
+        stream = torch.cuda.current_stream(where).cuda_stream
+        dev = scene._device_scene(device)
+        colour = torch.empty((self.height, self.width, 3), dtype=torch.float64, device=where)
+        aov = {name: torch.empty((self.height, self.width, 3)[: 3 if ch > 1 else 2], dtype=torch.float64, device=where)
+               for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1))}
+        rgba = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device=where)
+        if self.height * self.width > 0:
+            dev.render_async(self.Camera._state, params, colour.data_ptr(), None, stream)
+            dev.render_aov_async(self.Camera._state, params, aov["albedo"].data_ptr(), aov["normal"].data_ptr(),
+                                 aov["depth"].data_ptr(), stream=stream)
+            out = self._denoise_device(torch, colour, aov, overrides)
+            _lib.linear_to_srgba_async(out.data_ptr(), self.height * self.width, rgba.data_ptr(), device, stream)
+            self.linear[:] = out.cpu().numpy()
+        self.imageData[:] = rgba.cpu().numpy()
+        return self.imageData
 
     def RenderLines(self, idx: int, yStart: int, yEnd: int, scene: Scene) -> None:  # ray/tracer.go:120-155
         """Render rows [yStart, yEnd) with the current (initialized) camera and
