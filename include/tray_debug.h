@@ -56,6 +56,11 @@ extern "C" {
 int tray_debug_set(const char *name, int64_t value);
 /* Unsets knob `name`, or every knob when name is NULL. */
 int tray_debug_clear(const char *name);
+/* The device's progress counters as the last tray_render_progress on `device` left them:
+ * finished samples per 8-row tile row of the render's rows, as the kernel counted them (the
+ * host polls the same words while the launch runs). Writes min(*n_out, capacity) counters;
+ * *n_out is the number of tile rows, 0 before any such render. */
+int tray_debug_progress_counts(int32_t device, uint64_t *counts, int32_t capacity, int32_t *n_out);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-phase ISA census of the BVH megakernel (render_kernel<1,true,false,false,false,true,5>).
+"""Per-phase ISA census of the BVH megakernel (render_kernel<1,true,false,false,false,1,5>).
 
 Builds tray_kernel.hip for gfx950 with the product flags plus -g (debug line
 tables do not change the generated code: the census checks the instruction
@@ -8,8 +8,9 @@ symbolises every instruction with its inline stack. The frame of
 render_kernel gives the source line of the kernel loop the instruction belongs
 to; the TRAY_MARK anchors in tray_kernel.hip (no-ops in every build but
 -DTRAY_CENSUS) divide the loop into phases: refill (item assignment, camera
-ray, candidate tests, shading of candidate-answered camera rays), node steps,
-leaf tests, shading. Each VALU instruction is classed as the SQ_INSTS_VALU_*
+ray, candidate tests, the end half of the shading of candidate-answered camera
+rays), the scatter step with its begin part, node steps, leaf tests, the shade
+phase (the end half). Each VALU instruction is classed as the SQ_INSTS_VALU_*
 counters class it (FP64 add/mul/fma, FP32, transcendental, INT32, INT64,
 conversion) or, for the ~42 % those counters do not cover, by what it is
 (moves, v_cndmask, compares, min/max, lane ops, bit ops that are not INT32
@@ -38,7 +39,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tray_amd", "csrc", "tray_kernel.hip")
-KERNEL = "_ZN4tray13render_kernelILi1ELb1ELb0ELb0ELb0ELi1ELi5EEEvNS_12KernelParamsE"  # --layout 2: ...ILi2E...
+KERNEL = "_ZN4tray13render_kernelILi1ELb1ELb0ELb0ELb0ELi1ELi5ELb0EEEvNS_12KernelParamsE"  # --layout 2: ...ILi2E...
 LLVM = "/opt/rocm/lib/llvm/bin"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-mllvm",
          "-amdgpu-atomic-optimizer-strategy=None"]
@@ -161,7 +162,9 @@ def symbolize(co: str, insts):
     stacks = []
     for line in out.splitlines():
         rec = json.loads(line)
-        stacks.append([(f["FunctionName"], int(f["Line"])) for f in rec["Symbol"]])
+        # a lambda's name carries its absolute source path: keep the line only
+        stacks.append([(re.sub(r"\(lambda at [^)]*?:(\d+):\d+\)", r"(lambda:\1)", f["FunctionName"]), int(f["Line"]))
+                       for f in rec["Symbol"]])
     assert len(stacks) == len(insts)
     return stacks
 
@@ -186,12 +189,14 @@ def phase_of(line: int, marks) -> str:
 
 # Which phase-profile counter counts the executions of each phase (per frame).
 WEIGHT = {"refill_assign": "loop_iters", "refill_cam": "refill_phases", "refill_cand": "refill_phases",
-          "refill_shade": "refill_phases", "begin": "begin_steps", "refill_end": "loop_iters",
-          "begin_end": "loop_iters", "node_ctl": "node_iters", "node": "node_iters",
+          "refill_shade": "refill_end_phases", "refill_end": "loop_iters",
+          "scatter_ctl": "scatter_steps", "scatter": "scatter_steps", "begin": "begin_steps",
+          "begin_end": "loop_iters", "scatter_end": "loop_iters", "node_ctl": "node_iters", "node": "node_iters",
           "leaf_decide": "loop_iters", "leaf_ctl": "leaf_phases", "leaf": "leaf_phases",
           "shade_ctl": "shade_phases", "shade": "shade_phases", "shade_end": "shade_phases"}
-GROUP = {"refill_assign": "refill", "refill_cam": "refill", "refill_cand": "refill", "refill_shade": "refill",
-         "begin": "refill", "refill_end": "loop", "begin_end": "loop", "node_ctl": "node", "node": "node",
+GROUP = {"refill_assign": "refill", "refill_cam": "refill", "refill_cand": "refill", "refill_shade": "refill_end",
+         "refill_end": "loop", "scatter_ctl": "scatter", "scatter": "scatter", "begin": "begin",
+         "begin_end": "loop", "scatter_end": "loop", "node_ctl": "node", "node": "node",
          "leaf_decide": "loop", "leaf_ctl": "leaf",
          "leaf": "leaf", "shade_ctl": "shade", "shade": "shade", "shade_end": "shade"}
 
@@ -276,14 +281,18 @@ def main():
             if ph not in static:
                 continue
             n = pr.get(w, 0)
+            if ph in ("node_ctl", "node"):
+                # the phase's static code is all the unrolled node steps (kSteps copies), and
+                # node_iters counts every step executed: one copy per count
+                n /= int(re.search(r"Li(\d+)ELb[01]EEEv", KERNEL).group(1))
             for k, v in static[ph].items():
                 if k == "valu" or k.startswith("c:"):
                     dyn[k] += v * n
                     dyn_group[GROUP[ph]][k] += v * n
         est = {"source": os.path.relpath(args.phase, ROOT), "weights": {ph: WEIGHT[ph] for ph in WEIGHT},
-               "valu_per_frame": dyn["valu"],
-               "classes_per_frame": {k[2:]: v for k, v in sorted(dyn.items()) if k.startswith("c:")},
-               "by_group": {g: {"valu": c["valu"], **{k[2:]: v for k, v in sorted(c.items()) if k.startswith("c:")}}
+               "valu_per_frame": round(dyn["valu"]),
+               "classes_per_frame": {k[2:]: round(v) for k, v in sorted(dyn.items()) if k.startswith("c:")},
+               "by_group": {g: {"valu": round(c["valu"]), **{k[2:]: round(v) for k, v in sorted(c.items()) if k.startswith("c:")}}
                             for g, c in dyn_group.items()}}
         tot = max(1, dyn["valu"])
         est["uncounted_share"] = round(sum(dyn["c:" + c] for c in UNCOUNTED) / tot, 3)

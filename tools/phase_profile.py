@@ -10,7 +10,9 @@ import json
 import os
 import sys
 
-PHASES = ("cyc_refill", "cyc_node", "cyc_leaf", "cyc_shade")
+# Disjoint stamp pairs. cyc_refill includes cyc_refill_end (the end half of the refill's camera-hit
+# shading); cyc_scatter is the scatter step without its begin part, cyc_begin that part.
+PHASES = ("cyc_refill", "cyc_scatter", "cyc_begin", "cyc_node", "cyc_leaf", "cyc_shade")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -22,10 +24,10 @@ def main():
     ap.add_argument("--shard", default=None, help="N,K: rank K's row tiles of an N-way split (1-row tiles)")
     ap.add_argument("--refill-split", action="store_true", help="the library is a -DTRAY_PROFILE_REFILL build")
     ap.add_argument("--begin", action="store_true",
-                    help="the library is a -DTRAY_PROFILE_BEGIN build: report the begin-step census")
+                    help="the library is a -DTRAY_PROFILE_BEGIN build: report where the scatter step's lanes were marked")
     ap.add_argument("--waves", type=int, default=256 * 16, help="waves in the launch (CUs x waves per CU)")
     ap.add_argument("--material", action="store_true",
-                    help="the library is a -DTRAY_PROFILE_MATERIAL build: report the shading divergence census")
+                    help="the library is a -DTRAY_PROFILE_MATERIAL build: report the scatter step's divergence census")
     args = ap.parse_args()
     import torch
 
@@ -48,7 +50,7 @@ def main():
                              torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     allv = stats.tolist()
-    v = allv[:22]
+    v = allv[:30]
     # -DTRAY_PROFILE_REFILL: stats[13], [16], [17], [18] (slots 10, 13-15) hold the refill split
     refill_split = dict(zip(["refill_assign", "refill_camera", "refill_hit", "refill_shade"],
                             [allv[13], allv[16], allv[17], allv[18]]))
@@ -56,24 +58,25 @@ def main():
     names = ["segments", "sphere_tests", "box_tests", "cyc_refill", "cyc_node", "cyc_leaf", "cyc_shade",
              "node_iters", "node_lanes", "leaf_phases", "leaf_lanes", "shade_phases", "shade_lanes", "loop_iters", "node_leafwait_lanes", "node_shadewait_lanes", "refill_phases", "refill_lanes",
              "begin_steps", "rt_end_max", "rt_life_sum",
-             "rt_start_min_inv"]
+             "rt_start_min_inv", "cyc_refill_end", "refill_end_phases", "refill_end_lanes", "cyc_scatter",
+             "scatter_steps", "scatter_lanes", "absorbed_lanes", "cyc_begin"]
     d = dict(zip(names, v))
     if args.refill_split:
         d["refill_split_share"] = {k: round(x / max(1, d["cyc_refill"]), 3) for k, x in refill_split.items()}
-    if args.begin:  # slots 10-12 hold the begin-step census: (passes << 40) + lanes
+    if args.begin:  # slots 10-12 hold the census of the scatter step's sources: (passes << 40) + lanes
         lo = (1 << 40) - 1
         sh, rf, bg = d.pop("loop_iters"), d.pop("node_leafwait_lanes"), d.pop("node_shadewait_lanes")
         d["begin"] = {
-            "readied_by_shade": {"passes": sh >> 40, "lanes": sh & lo},
-            "readied_by_refill_shade": {"passes": rf >> 40, "lanes": rf & lo},
-            "begin_steps": d["begin_steps"], "begin_lanes": bg & lo,
-            "refills_after_a_scattering_shade_pass": bg >> 40,
+            "marked_by_shade": {"passes": sh >> 40, "lanes": sh & lo},
+            "marked_by_refill_shade": {"passes": rf >> 40, "lanes": rf & lo},
+            "scatter_steps": d["scatter_steps"], "scatter_lanes": bg & lo, "begin_steps": d["begin_steps"],
+            "refills_after_a_marking_shade_pass": bg >> 40,
         }
         b = d["begin"]
-        b["lanes_per_begin_step"] = round(b["begin_lanes"] / max(1, b["begin_steps"]), 1)
+        b["lanes_per_scatter_step"] = round(b["scatter_lanes"] / max(1, b["scatter_steps"]), 1)
         b["lanes_per_shade_site_pass"] = round((sh & lo) / max(1, sh >> 40), 1)
         b["lanes_per_refill_site_pass"] = round((rf & lo) / max(1, rf >> 40), 1)
-        b["begin_calls_saved"] = (sh >> 40) + (rf >> 40) - b["begin_steps"]
+        b["scatter_calls_saved"] = (sh >> 40) + (rf >> 40) - b["scatter_steps"]
         b["refills_adjacent_share"] = round((bg >> 40) / max(1, d["refill_phases"]), 3)
         for k in ("loop_iters", "node_leafwait_lanes", "node_shadewait_lanes"):
             d[k] = 0
@@ -89,6 +92,11 @@ def main():
     d["cyc_per_node_iter"] = round(d["cyc_node"] / max(1, d["node_iters"]), 1)
     d["cyc_per_leaf_phase"] = round(d["cyc_leaf"] / max(1, d["leaf_phases"]), 1)
     d["cyc_per_shade_phase"] = round(d["cyc_shade"] / max(1, d["shade_phases"]), 1)
+    d["lanes_per_refill_end_phase"] = round(d["refill_end_lanes"] / max(1, d["refill_end_phases"]), 1)
+    d["cyc_per_refill_end_phase"] = round(d["cyc_refill_end"] / max(1, d["refill_end_phases"]), 1)
+    d["lanes_per_scatter_step"] = round(d["scatter_lanes"] / max(1, d["scatter_steps"]), 1)
+    d["cyc_per_scatter_step"] = round(d["cyc_scatter"] / max(1, d["scatter_steps"]), 1)
+    d["cyc_per_begin_step"] = round(d["cyc_begin"] / max(1, d["begin_steps"]), 1)
     # Tail: kernel span (latest exit - earliest start) vs the mean wave lifetime,
     # on the 100 MHz constant-rate clock (s_memrealtime).
     start_min = (1 << 64) - 1 - (d["rt_start_min_inv"] % (1 << 64))
@@ -109,7 +117,8 @@ def main():
     if args.material:
         cls = ["miss", "last", "lambertian", "metal0", "metal_fuzz", "dielectric"]
         mat = allv[32 + 2 * args.waves:]
-        for site, name in enumerate(["refill_shade", "shade"]):
+        # the scatter step's lanes by where they were marked
+        for site, name in enumerate(["scatter_from_refill", "scatter_from_shade"]):
             c = mat[26 * site: 26 * site + 26]
             passes = max(1, c[16])
             d["material_" + name] = {

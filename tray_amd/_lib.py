@@ -251,7 +251,7 @@ class DenoiseParams(ctypes.Structure):
 assert ctypes.sizeof(DenoiseGuides) == 24 and ctypes.sizeof(DenoiseParams) == 40
 
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
-DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear")
+DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear", "tray_debug_progress_counts")
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
                "primary_candidates", "resolve_staged", "wave_chunks", "scene_contexts", "grid_reserve",
                "work_order", "coop_lanes")
@@ -353,6 +353,9 @@ def lib(path: str | None = None) -> ctypes.CDLL:
     if hasattr(L, "tray_debug_set"):  # absent from older builds (A/B tools)
         L.tray_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
         L.tray_debug_clear.argtypes = [ctypes.c_char_p]
+    if hasattr(L, "tray_debug_progress_counts"):
+        L.tray_debug_progress_counts.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
+                                                 ctypes.POINTER(ctypes.c_int32)]
     _libs[path] = L
     return L
 
@@ -385,6 +388,18 @@ def set_debug_knobs(lib_path: str | None = None, **knobs) -> dict:
         if rc != TRAY_OK:
             raise TrayError(rc, L.tray_last_error().decode())
     return before
+
+
+def progress_counts(device: int = 0) -> np.ndarray:
+    """tray_debug_progress_counts: finished samples per 8-row tile row as the kernel counted them
+    during the last render(..., progress=...) on `device`."""
+    n = ctypes.c_int32(0)
+    check(lib().tray_debug_progress_counts(device, None, 0, ctypes.byref(n)))
+    counts = np.zeros(n.value, dtype=np.uint64)
+    if n.value:
+        check(lib().tray_debug_progress_counts(device, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n.value,
+                                               ctypes.byref(n)))
+    return counts
 
 
 def clear_debug_knobs(lib_path: str | None = None) -> None:

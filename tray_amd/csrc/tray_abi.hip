@@ -85,6 +85,7 @@ struct Slot {
     unsigned long long* prog_host = nullptr;
     unsigned long long* prog_dev = nullptr;  // its device address
     size_t prog_bytes = 0;
+    int32_t prog_tile_rows = 0;  // counters of the last progress render (tray_debug_progress_counts)
 };
 
 // Per-device state: render slots and the sRGB encoder table of
@@ -314,6 +315,18 @@ int tray_debug_clear(const char* name) {
     const int i = knob_index(name);
     if (i < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, std::string("unknown debug knob: ") + name);
     g_knob_set[i].store(false, std::memory_order_release);
+    return TRAY_OK;
+}
+
+int tray_debug_progress_counts(int32_t device, uint64_t* counts, int32_t capacity, int32_t* n_out) {
+    if (!n_out || (capacity > 0 && !counts) || capacity < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "null argument");
+    DeviceState* st = nullptr;
+    const int rc = device_state(device, &st);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(st->mu);
+    const Slot& sl = st->slot(0);  // tray_render_progress renders through slot 0; it has returned, so the stream is idle
+    *n_out = sl.prog_host ? sl.prog_tile_rows : 0;
+    for (int32_t t = 0; t < *n_out && t < capacity; ++t) counts[t] = (uint64_t)sl.prog_host[t];
     return TRAY_OK;
 }
 
@@ -1133,6 +1146,7 @@ static hipError_t prepare_progress(Slot& sl, int32_t rows) {
         sl.prog_bytes = bytes;
     }
     memset(sl.prog_host, 0, bytes);
+    sl.prog_tile_rows = (rows + 7) / 8;
     return hipSuccess;
 }
 

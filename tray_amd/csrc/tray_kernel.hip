@@ -413,8 +413,10 @@ __device__ __forceinline__ float f32_up(double v) {
 // per-step state bookkeeping): an inner node (< kBvhLeafBit) = traversing; a
 // leaf reference = waiting for the leaf phase; kBvhNone = traversal done,
 // waiting for the shade phase (busy lane) or idle (Lane::busy false);
-// kTravReady = the ray of a new segment is in Lane::org / dir and its setup
-// (trav_begin) is still to run, in the kernel loop's begin step.
+// kTravHit / kTravHitCam = the finished segment hit a sphere above the last level
+// (Trav::slot, closest and a still describe the hit): its scatter (shade_scatter) is
+// still to run, in the kernel loop's scatter step; kTravReady = the scattered ray is in
+// Lane::org / dir and its setup (trav_begin) is still to run, in that step's begin part.
 
 struct Trav {
     float ix, iy, iz, oix, oiy, oiz;  // FP32 ray: t = box * inv - org * inv
@@ -476,7 +478,10 @@ __device__ __forceinline__ float key_tn(uint32_t key) { return __uint_as_float(k
 
 // Above every child reference and kBvhNone: neither is_trav nor is_leaf, not waiting
 // for the shade phase (cur == kBvhNone) and not work in flight (cur < kBvhNone).
-constexpr uint32_t kTravReady = kBvhNone + 1u;
+// kTravHit / kTravHitCam: marked by the shade phase / by the refill's camera-hit shading
+// (told apart only by the material census of the profile build); is_marked covers both.
+constexpr uint32_t kTravReady = kBvhNone + 1u, kTravHit = kBvhNone + 2u, kTravHitCam = kBvhNone + 3u;
+__device__ __forceinline__ bool is_marked(uint32_t cur) { return cur > kTravReady; }
 __device__ __forceinline__ bool is_trav(uint32_t cur) { return cur < kBvhLeafBit; }
 __device__ __forceinline__ bool is_leaf(uint32_t cur) { return cur - kBvhLeafBit < kBvhNone - kBvhLeafBit; }
 
@@ -525,7 +530,7 @@ __device__ __forceinline__ void trav_globals(Trav& T, const SceneView& sv, const
 // freely (pinhole: proportional to FocalLength; lens: about FocusDistance), and a
 // caller's ray has any length. Whoever calls trav_begin32 answers for the range: the ray
 // queries send any other ray through the linear scan (query_hit), the megakernel tests
-// every tree sphere for such a camera ray (the refill), and the begin step's rays are
+// every tree sphere for such a camera ray (the refill), and the scatter step's rays are
 // scattered ones, of order one (Metal and Dielectric start from Unit(direction),
 // Lambertian from a unit normal plus a unit vector with NearZero replaced).
 __device__ __forceinline__ bool slab_dir_ok(double a) { return a >= 1e-30 && a <= 1e30; }
@@ -1026,18 +1031,23 @@ __device__ __forceinline__ uint64_t acc_retire(const KernelParams& p, const AccC
 }
 
 // One recursion level of RayColor (ray/objects.go:49-62) after Scene.Hit gave
-// (best, closest): the sky on a miss, else the hit record and the material's
-// scatter. `geo_at`/`mat_at` give the hit sphere's geometry and shading record.
-// Returns true when the lane has a scattered ray to trace, false when the path
-// ended (stored; the lane is free).
-//
-// Written for a wave of lanes on different branches: the work several branches
-// need is done once, before them — the bounce's draw block and the unit
-// direction (sky, Metal, Dielectric).
-template <bool kStats, int kAcc, bool kWild, typename GeoAt, typename MatAt>
-__device__ __forceinline__ bool shade_step(const KernelParams& p, Lane& L, int best, double closest,
-                                           double dir_lsq, GeoAt geo_at, MatAt mat_at, Stats& st, const AccCtx& acc) {
-    const bool hit = best >= 0;
+// (best, closest), in two halves with the per-lane arithmetic of the one function they
+// were: shade_end for a lane whose path ends without a scatter (the sky on a miss, black
+// at the last level), shade_scatter for every other hit (the hit record and the
+// material's scatter). shade_step composes them for the linear scan; the BVH loop runs
+// shade_end where a lane's traversal ends and shade_scatter once per iteration, in its
+// scatter step, for the hits of both its shading sites together.
+
+// Each half has a colour function, which leaves the lane's path open and gives the colour
+// it ends with, and a wrapper that ends the path (end_path): the BVH loop calls the
+// wrappers, shade_step the colour functions, so that it holds one end_path as it always did.
+
+// The end half. Returns true for a hit that shade_scatter is still to serve (the lane is
+// untouched), false when the path ends here with `color`. It reads no shading record and
+// draws nothing, so it leaves nothing in flight for end_path's stores.
+template <bool kWild>
+__device__ __forceinline__ bool shade_end_color(const KernelParams& p, const Lane& L, bool hit, double dir_lsq,
+                                                D3& color) {
     // A hit at the last level ends the path black whatever its material does
     // (RayColor(depth 0) is black), so no scatter is computed for it.
     const bool last = L.bounce + 1u >= (uint32_t)p.max_depth;
@@ -1046,28 +1056,53 @@ __device__ __forceinline__ bool shade_step(const KernelParams& p, Lane& L, int b
     // (Mul(attenuation, RayColor(...)), ray/objects.go:56), the last level's too
     // when its material scatters, and inf * 0 and NaN * 0 are NaN. In such a
     // scene a last-level hit therefore scatters like any other hit and the
-    // black is multiplied (below). In every other scene those products are
+    // black is multiplied (shade_scatter). In every other scene those products are
     // zeros and are not formed.
     const bool blind = kWild ? false : last;  // a last-level hit whose scatter cannot show
-    bool ends = !hit || last;
-    // Issued first, for every lane (a miss reads a valid record it ignores), so
-    // the L2 round trip of the shading record overlaps the FP64 work below
-    // instead of starting after it inside the hit branch.
+    if (hit && !blind) return true;
+    color = d3(0, 0, 0);
+    if (!hit) {  // AmbientLight.Hit (ray/objects.go:68-73)
+        const D3 ud = unit_lsq(L.dir, dir_lsq);  // dir_lsq = length_sq(L.dir)
+        const double t = 0.5 * (ud.y + 1.0);
+        const D3 bg_a = d3(p.bg_a.x, p.bg_a.y, p.bg_a.z), bg_b = d3(p.bg_b.x, p.bg_b.y, p.bg_b.z);
+        color = mul(L.thr, add(smul(bg_a, 1.0 - t), smul(bg_b, t)));
+    }
+    return false;
+}
+// Returns false when the path ended here (stored; the lane is free).
+template <bool kStats, int kAcc, bool kWild>
+__device__ __forceinline__ bool shade_end(const KernelParams& p, Lane& L, bool hit, double dir_lsq, Stats& st,
+                                          const AccCtx& acc) {
+    D3 color;
+    if (shade_end_color<kWild>(p, L, hit, dir_lsq, color)) return true;
+    end_path<kStats, kAcc>(p, L, color, st, acc);
+    return false;
+}
+
+// The scatter half, for a hit that shade_end returned true for. `geo_at`/`mat_at` give the
+// hit sphere's geometry and shading record. Returns true when the lane has a scattered ray
+// to trace, false when the path ends with `color` (absorbed).
+//
+// Written for a wave of lanes on different branches: the work several branches
+// need is done once, before them — the bounce's draw block and the unit
+// direction (Metal, Dielectric).
+template <bool kWild, typename GeoAt, typename MatAt>
+__device__ __forceinline__ bool shade_scatter_color(const KernelParams& p, Lane& L, double closest, double dir_lsq,
+                                                    GeoAt geo_at, MatAt mat_at, D3& color) {
+    // Issued first, so the L2 round trip of the shading record overlaps the draw block
+    // instead of starting after it.
     const double4 g = geo_at();
     const MatRec m = mat_at();
     const Block w = draw(p, L.pixel, L.sample, L.bounce, kPurposeScatter);
     const double u0 = uniform(w.x0);
-    // Unit(r.Direction) is read by the sky, Metal and Dielectric, not by Lambertian
-    // (nor a last-level hit): a wave whose shading lanes are all Lambertian hits
-    // (a camera-ray pass of a diffuse pixel) skips the sqrt and three quotients.
+    // Unit(r.Direction) is read by Metal and Dielectric, not by Lambertian: a wave whose
+    // lanes are all Lambertian hits (the camera rays of a diffuse pixel) skips the sqrt
+    // and three quotients.
     D3 ud = d3(0, 0, 0);
-    if (!hit || (!blind && m.type != kLambertian)) ud = unit_lsq(L.dir, dir_lsq);  // dir_lsq = length_sq(L.dir)
-    D3 color = d3(0, 0, 0);
-    if (!hit) {  // AmbientLight.Hit (ray/objects.go:68-73)
-        const double t = 0.5 * (ud.y + 1.0);
-        const D3 bg_a = d3(p.bg_a.x, p.bg_a.y, p.bg_a.z), bg_b = d3(p.bg_b.x, p.bg_b.y, p.bg_b.z);
-        color = mul(L.thr, add(smul(bg_a, 1.0 - t), smul(bg_b, t)));
-    } else if (!blind) {
+    if (m.type != kLambertian) ud = unit_lsq(L.dir, dir_lsq);  // dir_lsq = length_sq(L.dir)
+    color = d3(0, 0, 0);
+    bool ends = false;
+    {
         const D3 point = add(L.org, smul(L.dir, closest));                             // Ray.At (ray/ray.go:23-25)
         const D3 outward = sdiv_rcp(sub(point, d3(g.x, g.y, g.z)), m.radius, m.rinv);  // ray/objects.go:100
         const bool front = dot(L.dir, outward) < 0;                                    // SetFaceNormal (:19-26)
@@ -1098,7 +1133,8 @@ __device__ __forceinline__ bool shade_step(const KernelParams& p, Lane& L, int b
             const bool do_reflect = ratio * sin_theta > 1.0 || reflectance(cos_theta, r0) > u0;
             new_dir = do_reflect ? reflect(ud, normal) : refract(ud, normal, ratio);
         }
-        if (scattered && (kWild ? !last : true)) {
+        // kWild: a last-level hit scatters into depth 0, which is black (shade_end).
+        if (scattered && (kWild ? L.bounce + 1u < (uint32_t)p.max_depth : true)) {
             L.thr = mul(L.thr, att);
             L.org = point;
             L.dir = new_dir;
@@ -1112,7 +1148,28 @@ __device__ __forceinline__ bool shade_step(const KernelParams& p, Lane& L, int b
     // counter, so a load still pending when end_path stores would make the next
     // write of its registers wait for the stores' write-back too.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    if (!ends) return true;
+    return !ends;
+}
+// Returns false when the path ended here (absorbed: stored; the lane is free).
+template <bool kStats, int kAcc, bool kWild, typename GeoAt, typename MatAt>
+__device__ __forceinline__ bool shade_scatter(const KernelParams& p, Lane& L, double closest, double dir_lsq,
+                                              GeoAt geo_at, MatAt mat_at, Stats& st, const AccCtx& acc) {
+    D3 color;
+    if (shade_scatter_color<kWild>(p, L, closest, dir_lsq, geo_at, mat_at, color)) return true;
+    end_path<kStats, kAcc>(p, L, color, st, acc);
+    return false;
+}
+
+// Both halves on one lane set (the linear scan, whose Scene.Hit is the whole iteration).
+// Returns true when the lane has a scattered ray to trace, false when the path ended.
+template <bool kStats, int kAcc, bool kWild, typename GeoAt, typename MatAt>
+__device__ __forceinline__ bool shade_step(const KernelParams& p, Lane& L, int best, double closest,
+                                           double dir_lsq, GeoAt geo_at, MatAt mat_at, Stats& st, const AccCtx& acc) {
+    D3 color;
+    bool goes_on = false;
+    if (shade_end_color<kWild>(p, L, best >= 0, dir_lsq, color))
+        goes_on = shade_scatter_color<kWild>(p, L, closest, dir_lsq, geo_at, mat_at, color);
+    if (goes_on) return true;
     end_path<kStats, kAcc>(p, L, color, st, acc);
     return false;
 }
@@ -1204,13 +1261,17 @@ constexpr int32_t kDeepNodes = 384;
 
 // Diagnostic build only (-DTRAY_PROFILE): per-wave s_memtime stamps around each
 // phase of the BVH loop, plus phase and active-lane counts, added into
-// stats[3..21] (the stats buffer must then hold 22 counters). Never part of a
+// stats[3..29] (the stats buffer must then hold 30 counters). Never part of a
 // timed build: the stamps' waits serialise the phases.
-// With -DTRAY_PROFILE_BEGIN the census of the begin step replaces slots 10-12
-// (tools/phase_profile.py --begin): [10] / [11] segments readied by the shade phase /
+// Slots 0-15 go to stats[3..18], slots 16-23 to stats[22..29]: [16] cycles, [17] passes,
+// [18] lanes of the refill's end half (its cycles are inside slot 0's too); [19] cycles,
+// [20] passes, [21] lanes of the scatter step's scatter part; [22] lanes absorbed in it;
+// [23] cycles of its begin part.
+// With -DTRAY_PROFILE_BEGIN the census of the scatter step's sources replaces slots 10-12
+// (tools/phase_profile.py --begin): [10] / [11] hits marked by the shade phase /
 // by the refill's camera-hit shading, as (passes << 40) + lanes; [12] (refills that
-// found segments readied by the shade phase just before << 40) + lanes of the begin
-// steps. Slot 15 counts the begin steps in every profile build.
+// found lanes marked by the shade phase just before << 40) + lanes of the scatter
+// steps. Slot 15 counts the scatter steps that begin a segment in every profile build.
 #ifdef TRAY_PROFILE
 // Counters live in LDS (per wave, lane 0 adds): registers would change the
 // kernel being measured.
@@ -1221,6 +1282,9 @@ constexpr int32_t kDeepNodes = 384;
         const unsigned long long v_ = (v);                 \
         if (lane == 0) atomicAdd(prof + (slot), v_);       \
     }
+// A stamp pair nested in another phase's, or on a slot the timeline build has none for.
+#define PROF_T0E() PROF_T0()
+#define PROF_ADDE(slot) PROF_ADD(slot)
 #elif defined(TRAY_PROFILE_TIMELINE)
 // The timeline build times the phases of a wave's lone last path (refill, node steps,
 // leaves, shading: tl_ph[0..3]).
@@ -1233,12 +1297,16 @@ constexpr int32_t kDeepNodes = 384;
 #define PROF_ADD(slot)
 #define PROF_CNT(slot, v)
 #endif
+#ifndef TRAY_PROFILE
+#define PROF_T0E()
+#define PROF_ADDE(slot)
+#endif
 
 // Diagnostic build only (-DTRAY_PROFILE -DTRAY_PROFILE_MATERIAL): the divergence
-// census of the shading passes. Per site (0: camera-ray hits shaded in the
-// refill, 1: the shade phase) and per class of shaded lane (0 miss/sky, 1 hit at
-// the last level, 2 Lambertian, 3 Metal without fuzz, 4 Metal with fuzz, 5
-// Dielectric): [c] passes with such a lane, [6 + c] such lanes; [12 + b] passes
+// census of the scatter step's passes. Per site (the marked lanes that come 0: from
+// the refill's camera-hit shading, 1: from the shade phase) and per class of lane (0
+// miss/sky and 1 hit at the last level: none since the end half serves them, 2
+// Lambertian, 3 Metal without fuzz, 4 Metal with fuzz, 5 Dielectric): [c] passes with such a lane, [6 + c] such lanes; [12 + b] passes
 // executing b of the three material bodies (b = 0..3); [16] passes, [17] lanes;
 // [18 + h] / [22 + h] passes with 1, 2-3, 4-7, >= 8 Dielectric / Metal lanes.
 // Added with global atomics after the per-wave stamps (stats[32 + 2 x waves + k]).
@@ -1269,12 +1337,13 @@ __device__ __forceinline__ void prof_material(int site, bool active, int32_t slo
     }
     bodies = (__ballot(cls == 2) ? 1 : 0) + (__ballot(cls == 3 || cls == 4) ? 1 : 0) + (__ballot(cls == 5) ? 1 : 0);
     const int n_di = __popcll(__ballot(cls == 5)), n_me = __popcll(__ballot(cls == 3 || cls == 4));
+    const int n_active = __popcll(__ballot(active));  // ahead of the branch: inside it only lane 0 votes
     if (lane == 0) {
         if (n_di) atomicAdd(c + 18 + (n_di >= 8 ? 3 : n_di >= 4 ? 2 : n_di >= 2 ? 1 : 0), 1ull);
         if (n_me) atomicAdd(c + 22 + (n_me >= 8 ? 3 : n_me >= 4 ? 2 : n_me >= 2 ? 1 : 0), 1ull);
         atomicAdd(c + 12 + bodies, 1ull);
         atomicAdd(c + 16, 1ull);
-        atomicAdd(c + 17, (unsigned long long)__popcll(__ballot(active)));
+        atomicAdd(c + 17, (unsigned long long)n_active);
     }
 }
 #define PROF_MATERIAL(site, active) prof_material(site, active, T.slot, L.bounce, p.max_depth, p.bmat, lane, prof_mat)
@@ -1424,10 +1493,10 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
     int32_t prog_cur = 0;  // live progress: the wave's current tile row and its unflushed count
     uint64_t prog_cnt = 0;
 #ifdef TRAY_PROFILE
-    __shared__ unsigned long long prof_lds[16 * 16];
-    unsigned long long* prof = prof_lds + 16 * (threadIdx.x / 64u);
+    __shared__ unsigned long long prof_lds[16 * 24];
+    unsigned long long* prof = prof_lds + 24 * (threadIdx.x / 64u);
     if (lane == 0)
-        for (int i = 0; i < 16; ++i) prof[i] = 0;
+        for (int i = 0; i < 24; ++i) prof[i] = 0;
     const uint64_t prof_start = __builtin_amdgcn_s_memrealtime();
 #endif
 #ifdef TRAY_PROFILE_MATERIAL  // counts only (global atomics: its timings are not used)
@@ -1571,7 +1640,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             PROF_CNT(13, fresh != 0ull ? 1 : 0);
             PROF_CNT(14, __popcll(fresh));
 #ifdef TRAY_PROFILE_BEGIN  // refills that find segments readied by the shade phase just before
-            if constexpr (kBVH) PROF_CNT(12, (uint64_t)(fresh != 0ull && __ballot(T.cur == kTravReady) != 0ull) << 40);
+            if constexpr (kBVH) PROF_CNT(12, (uint64_t)(fresh != 0ull && __ballot(T.cur == kTravHit) != 0ull) << 40);
 #endif
         }
 #endif
@@ -1647,28 +1716,29 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
 #endif
         // The refill's camera rays with a known hit are shaded at once (their
         // scattered rays join the node steps below) instead of waiting for the
-        // shade batch; the traversal lanes' batching is unchanged.
+        // shade batch; the traversal lanes' batching is unchanged. Here: the end half
+        // (sky, last level); a hit that scatters is marked for the scatter step below.
         if constexpr (kBVH) {
             if (__ballot(cam_hit) != 0ull) {
+                PROF_T0E();
                 TRAY_MARK("refill_shade")
-                PROF_MATERIAL(0, cam_hit);
                 bool ended = false;
                 if (cam_hit) {
-                    if (shade_step<kStats, kAcc, false>(kp_fresh(), L, T.slot, T.closest, T.a, [&] { return sv.bgeo[max(T.slot, 0)]; },
-                                                 [&] { return sv.bmat[max(T.slot, 0)]; }, st, acc)) {
-                        ++L.segments;
-                        T.cur = kTravReady;  // set up by the begin step below
-                    } else {
+                    if (shade_end<kStats, kAcc, false>(kp_fresh(), L, T.slot >= 0, T.a, st, acc))
+                        T.cur = kTravHitCam;
+                    else
                         ended = true;
-                    }
                 }
                 if constexpr (kProg) count_progress(p, ended, L.j, lane, prog_cur, prog_cnt);
 #ifdef TRAY_PROFILE_BEGIN
                 {
-                    const uint64_t m = __ballot(cam_hit && T.cur == kTravReady);
+                    const uint64_t m = __ballot(T.cur == kTravHitCam);
                     PROF_CNT(11, ((uint64_t)(m != 0ull) << 40) + (uint64_t)__popcll(m));
                 }
 #endif
+                PROF_ADDE(16);  // the refill's end half (also inside slot 0's refill time)
+                PROF_CNT(17, 1);
+                PROF_CNT(18, __popcll(__ballot(cam_hit)));
             }
         }
 #ifdef TRAY_PROFILE_REFILL
@@ -1720,32 +1790,85 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             }
             if constexpr (kProg) count_progress(p, ended, L.j, lane, prog_cur, prog_cnt);
         } else {
-            // Begin step: the setup of every new segment (trav_begin: |dir|^2 and its
+            // Scatter step: the scatter of every hit above the last level (shade_scatter: the
+            // shading record, the draw block, hit point and normal, the material bodies) and
+            // the setup of the scattered ray's segment (trav_begin: |dir|^2 and its
             // reciprocal, the out-of-tree spheres' Sphere.Hit, the FP32 traversal setup),
-            // once per iteration, for the rays scattered by the last shade phase and by the
-            // refill's camera-hit shading above together. The two used to set up their own
-            // lanes back to back (a shade phase frees the lanes that trigger the next
-            // refill), each on a minority of the wave; the same instructions now run once,
-            // on both sets.
-            // Invariant: a lane is kTravReady only from the end of the shade phase or of the
-            // refill's shading to this step, and this step leaves no lane in that state.
-            // Between them lie only loop control, the refill (which handles idle lanes) and
-            // the exit test above, which a ready lane fails (it is busy): the loop's exit,
-            // the drain, the node steps, the leaf phase and the shade phase never see the state.
+            // once per iteration, for the hits found by the last shade phase and by the
+            // refill's camera-hit shading above together. The two used to scatter and set
+            // up their own lanes back to back (a shade phase frees the lanes that trigger
+            // the next refill), each on a minority of the wave; the same instructions now
+            // run once, on both sets. A Metal ray absorbed here ends its path here, so its
+            // lane frees behind this iteration's refill and idles until the next one.
+            // Invariant: a lane is marked (kTravHit, kTravHitCam) only from the end of the
+            // shade phase or of the refill's end half to this step, and kTravReady (scattered,
+            // its segment not yet set up) only from this step's scatter part to its begin part
+            // right behind it: the step leaves no lane in any of the three states. Trav::slot, closest and a of the finished segment stay
+            // as the traversal left them until then: between the two lie only loop control,
+            // the refill (which handles idle lanes, and a marked lane is busy) and the exit
+            // test above, which a marked lane fails (it is busy): the loop's exit, the
+            // drain, the node steps, the leaf phase and the shade phase never see the state.
+            if (__ballot(is_marked(T.cur)) != 0ull) {
+                PROF_T0();
+                TRAY_MARK("scatter_ctl")
+                PROF_CNT(20, 1);
+                PROF_CNT(21, __popcll(__ballot(is_marked(T.cur))));
+#ifdef TRAY_PROFILE_BEGIN
+                PROF_CNT(12, __popcll(__ballot(is_marked(T.cur))));
+#endif
+                PROF_MATERIAL(0, T.cur == kTravHitCam);
+                PROF_MATERIAL(1, T.cur == kTravHit);
+                bool ended = false;
+                if (is_marked(T.cur)) {
+                    TRAY_MARK("scatter")
+#if defined(TRAY_STATS_GROUND) && !defined(TRAY_PROFILE)
+                    const bool from_g = T.slot >= sv.global_first;
+#endif
+                    if (shade_scatter<kStats, kAcc, false>(kp_fresh(), L, T.closest, T.a, [&] { return sv.bgeo[T.slot]; },
+                                                           [&] { return sv.bmat[T.slot]; }, st, acc)) {
+                        ++L.segments;
+#if defined(TRAY_STATS_GROUND) && !defined(TRAY_PROFILE)
+                        {
+                            const bool up = L.dir.y >= __builtin_fmax(__builtin_fabs(L.dir.x), __builtin_fabs(L.dir.z));
+                            gcls = from_g ? (up ? 1u : 2u) : 0u;
+                            if constexpr (kStats) {
+                                if (gcls == 1) ++st.g_seg[0];
+                                if (gcls != 0) ++st.g_seg[1];
+                            }
+                        }
+#endif
+                        T.cur = kTravReady;  // set up by the begin part below
+                    } else {
+                        ended = true;  // absorbed: the lane is idle
+                        T.cur = kBvhNone;
+                    }
+                }
+                if constexpr (kProg) count_progress(p, ended, L.j, lane, prog_cur, prog_cnt);
+                PROF_CNT(22, __popcll(__ballot(ended)));
+#ifdef TRAY_PROFILE
+                PROF_ADD(19);
+#else
+                PROF_ADD(3);  // the timeline build: counted with the shading
+#endif
+                TRAY_MARK("scatter_end")
+            }
+            // The begin part, in a block of its own: the compiler allocates the two apart
+            // without the SGPR spill the product instance has with them in one.
             {
                 PROF_T0();
 #if defined(TRAY_PROFILE) && !defined(TRAY_PROFILE_REFILL) && !defined(TRAY_PROFILE_CANDWAIT)  // (they time into slot 15)
                 PROF_CNT(15, __ballot(T.cur == kTravReady) != 0ull ? 1 : 0);
-#endif
-#ifdef TRAY_PROFILE_BEGIN
-                PROF_CNT(12, __popcll(__ballot(T.cur == kTravReady)));
 #endif
                 if (T.cur == kTravReady) {
                     TRAY_MARK("begin")
                     trav_begin(T, sv, L.org, L.dir);
                     if constexpr (kStats) st.spheres += (uint64_t)sv.n_global;
                 }
-                PROF_ADD(0);  // counted with the refill
+#ifdef TRAY_PROFILE
+                PROF_ADD(23);
+#else
+                PROF_ADD(0);  // the timeline build: counted with the refill
+#endif
                 TRAY_MARK("begin_end")
             }
             if constexpr (kLDS == 1) {
@@ -1852,7 +1975,6 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 TRAY_MARK("shade_ctl")
                 PROF_CNT(8, 1);
                 PROF_CNT(9, __popcll(m_shade));
-                PROF_MATERIAL(1, L.busy && T.cur == kBvhNone);
                 bool ended = false;
                 if (L.busy && T.cur == kBvhNone) {
                     TRAY_MARK("shade")
@@ -1862,29 +1984,17 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
 #ifdef TRAY_PROBE_SHADE64
                     TRAY_PROBE_F64(TRAY_PROBE_SHADE64)
 #endif
-                    if (shade_step<kStats, kAcc, false>(kp_fresh(), L, T.slot, T.closest, T.a, [&] { return sv.bgeo[max(T.slot, 0)]; },
-                                                 [&] { return sv.bmat[max(T.slot, 0)]; }, st, acc)) {
-                        ++L.segments;
-#if defined(TRAY_STATS_GROUND) && !defined(TRAY_PROFILE)
-                        {
-                            const bool from_g = T.slot >= sv.global_first;
-                            const bool up = L.dir.y >= __builtin_fmax(__builtin_fabs(L.dir.x), __builtin_fabs(L.dir.z));
-                            gcls = from_g ? (up ? 1u : 2u) : 0u;
-                            if constexpr (kStats) {
-                                if (gcls == 1) ++st.g_seg[0];
-                                if (gcls != 0) ++st.g_seg[1];
-                            }
-                        }
-#endif
-                        T.cur = kTravReady;  // set up by the begin step of the next iteration
-                    } else {
+                    // The end half (sky, last level); a hit that scatters is marked for the
+                    // scatter step of the next iteration.
+                    if (shade_end<kStats, kAcc, false>(kp_fresh(), L, T.slot >= 0, T.a, st, acc))
+                        T.cur = kTravHit;
+                    else
                         ended = true;  // idle: T.cur stays kBvhNone, L.busy is false
-                    }
                 }
                 if constexpr (kProg) count_progress(p, ended, L.j, lane, prog_cur, prog_cnt);
 #ifdef TRAY_PROFILE_BEGIN
                 {
-                    const uint64_t m = __ballot(T.cur == kTravReady);
+                    const uint64_t m = __ballot(T.cur == kTravHit);
                     PROF_CNT(10, ((uint64_t)(m != 0ull) << 40) + (uint64_t)__popcll(m));
                 }
 #endif
@@ -1941,6 +2051,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
 #ifdef TRAY_PROFILE
     if (kStats && lane == 0) {
         for (int i = 0; i < 16; ++i) atomicAdd(p.stats + 3 + i, (unsigned long long)prof[i]);
+        for (int i = 16; i < 24; ++i) atomicAdd(p.stats + 6 + i, (unsigned long long)prof[i]);
         // Wave lifetimes on the constant-rate clock: latest exit, sum of lifetimes, earliest start.
         const uint64_t end = __builtin_amdgcn_s_memrealtime();
         atomicMax(p.stats + 19, (unsigned long long)end);

@@ -30,7 +30,7 @@ constexpr int kBvhBlocksPerCU = 256 * TRAY_BVH_WAVES_PER_SIMD / TRAY_BVH_BLOCK;
 #define TRAY_COOP_LANES 2
 #endif
 #ifdef TRAY_PROFILE
-constexpr size_t kMaxLDSBytes = (160 * 1024) / kBvhBlocksPerCU - 2048;  // diagnostic builds: 2 KB of counters
+constexpr size_t kMaxLDSBytes = (160 * 1024) / kBvhBlocksPerCU - 3072;  // diagnostic builds: 3 KB of counters
 #else
 constexpr size_t kMaxLDSBytes = (160 * 1024) / kBvhBlocksPerCU;
 #endif
