@@ -6,6 +6,8 @@ have no meaning here).
     python -m tray_amd -ansi [-s 4] ...   # main.go's terminal view, non-interactive (-exit)
     python -m tray_amd -aov PREFIX ...    # also the first-hit feature buffers (include/tray_aov.h)
     python -m tray_amd -denoise -r 16 ... # the frame filtered on the device (include/tray_denoise.h)
+    python -m tray_amd -r 16 -passes 64 [-tolerance T] [-denoise] ...  # progressive: passes of -r rays until
+                                          # the frame has converged (include/tray_progressive.h)
 """
 from __future__ import annotations
 
@@ -47,6 +49,13 @@ def main(argv=None) -> int:
     ap.add_argument("-denoise", action="store_true",
                     help="save the frame after the guided a-trous filter (include/tray_denoise.h); "
                          "with -aov also PREFIX_denoised.png")
+    ap.add_argument("-passes", type=int, default=0, metavar="N",
+                    help="render progressively: up to N passes of -r rays each, folded on the device, until no "
+                         "pixel is left unconverged (include/tray_progressive.h); with -denoise the "
+                         "variance-guided filter")
+    ap.add_argument("-tolerance", type=float, default=None, metavar="T",
+                    help="with -passes: the relative standard error at which a pixel counts as converged "
+                         "(default: the library's, 0.05)")
     ap.add_argument("-ansi", action="store_true",
                     help="render at -s x the terminal size and draw it in the terminal (main.go:86-131)")
     ap.add_argument("-s", type=float, default=4, help="supersampling factor of -ansi")
@@ -58,11 +67,17 @@ def main(argv=None) -> int:
     t.NumRaysPerPixel, t.MaxDepth, t.Seed = a.r, a.d, a.seed
     scene = ray.RichScene(a.seed)
     t0 = time.perf_counter()
-    img = t.RenderDenoised(scene) if a.denoise else t.Render(scene)
+    if a.passes > 0:
+        img = t.RenderProgressive(scene, a.passes, tolerance=a.tolerance, denoise=a.denoise)
+        print(f"progressive: {t.passes} passes of r={a.r} done, {t.unconverged} of {a.width * a.height} pixels "
+              f"unconverged, worst relative error {t.max_ratio ** 0.5:.4g}")
+    else:
+        img = t.RenderDenoised(scene) if a.denoise else t.Render(scene)
     dt = time.perf_counter() - t0
     print(f"rendered {a.width}x{a.height} r={a.r} d={a.d}{' denoised' if a.denoise else ''} "
           f"({len(scene.Objects)} objects) in {dt:.3f} s: "
-          f"{a.width * a.height * a.r / dt / 1e6:.1f} Mrays/s end to end", file=sys.stderr)
+          f"{a.width * a.height * a.r * max(a.passes and t.passes, 1) / dt / 1e6:.1f} Mrays/s end to end",
+          file=sys.stderr)
     if a.save:
         png.save_png(a.save, img)
     if a.aov:

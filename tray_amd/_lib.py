@@ -250,6 +250,49 @@ class DenoiseParams(ctypes.Structure):
 
 assert ctypes.sizeof(DenoiseGuides) == 24 and ctypes.sizeof(DenoiseParams) == 40
 
+# Every symbol include/tray_progressive.h declares (the pass accumulator, its convergence
+# metric and the variance-guided filter; in none of the five lists above).
+PROGRESSIVE_EXPORTS = (
+    "tray_progressive_version",
+    "tray_accum_metric_default_params",
+    "tray_accum_fold_async",
+    "tray_accum_fold_metric_async",
+    "tray_denoise_variance_default_params",
+    "tray_denoise_variance_workspace_bytes",
+    "tray_denoise_variance_async",
+)
+
+
+class Accum(ctypes.Structure):
+    """tray_accum: the device state (mean, m2) and the host-side frame count."""
+    _fields_ = [("mean", ctypes.c_void_p), ("m2", ctypes.c_void_p), ("width", ctypes.c_int32),
+                ("rows", ctypes.c_int32), ("count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class AccumMetricParams(ctypes.Structure):
+    """tray_accum_metric_params."""
+    _fields_ = [("tolerance", ctypes.c_double), ("floor", ctypes.c_double)]
+
+
+class AccumMetric(ctypes.Structure):
+    """tray_accum_metric: the 16-byte device record."""
+    _fields_ = [("unconverged", ctypes.c_uint64), ("max_ratio", ctypes.c_double)]
+
+
+# tray_accum_metric as a numpy structured dtype, for reading the record back.
+ACCUM_METRIC_DTYPE = np.dtype([("unconverged", "<u8"), ("max_ratio", "<f8")])
+
+
+class DenoiseVarianceParams(ctypes.Structure):
+    """tray_denoise_variance_params."""
+    _fields_ = [("width", ctypes.c_int32), ("rows", ctypes.c_int32), ("iterations", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("sigma_variance", ctypes.c_double), ("sigma_normal", ctypes.c_double),
+                ("sigma_depth", ctypes.c_double), ("epsilon", ctypes.c_double)]
+
+
+assert ctypes.sizeof(Accum) == 32 and ctypes.sizeof(AccumMetricParams) == 16 and ctypes.sizeof(AccumMetric) == 16
+assert ctypes.sizeof(DenoiseVarianceParams) == 48 and ACCUM_METRIC_DTYPE.itemsize == 16
+
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
 DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear", "tray_debug_progress_counts")
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
@@ -350,6 +393,18 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.tray_denoise_workspace_bytes.argtypes = [ctypes.POINTER(DenoiseParams), ctypes.POINTER(ctypes.c_size_t)]
         L.tray_denoise_async.argtypes = [vp, ctypes.POINTER(DenoiseGuides), ctypes.POINTER(DenoiseParams), vp, vp,
                                          ctypes.c_size_t, i32, vp]
+    if hasattr(L, "tray_progressive_version"):  # include/tray_progressive.h; absent from older builds (A/B tools)
+        L.tray_progressive_version.restype = i32
+        L.tray_accum_metric_default_params.argtypes = [ctypes.POINTER(AccumMetricParams)]
+        L.tray_accum_fold_async.argtypes = [ctypes.POINTER(Accum), vp, i32, i32, vp]
+        L.tray_accum_fold_metric_async.argtypes = [ctypes.POINTER(Accum), vp, i32, ctypes.POINTER(AccumMetricParams),
+                                                   vp, vp, i32, vp]
+        L.tray_denoise_variance_default_params.argtypes = [i32, i32, ctypes.POINTER(DenoiseVarianceParams)]
+        L.tray_denoise_variance_workspace_bytes.argtypes = [ctypes.POINTER(DenoiseVarianceParams),
+                                                            ctypes.POINTER(ctypes.c_size_t)]
+        L.tray_denoise_variance_async.argtypes = [vp, vp, ctypes.POINTER(DenoiseGuides),
+                                                  ctypes.POINTER(DenoiseVarianceParams), vp, vp, vp, ctypes.c_size_t,
+                                                  i32, vp]
     if hasattr(L, "tray_debug_set"):  # absent from older builds (A/B tools)
         L.tray_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
         L.tray_debug_clear.argtypes = [ctypes.c_char_p]
@@ -607,6 +662,76 @@ def denoise_async(colour_ptr: int, params: DenoiseParams, out_ptr: int, workspac
                               int(workspace_bytes), int(device), stream)
     if rc != TRAY_OK:
         raise TrayError(rc, L.tray_last_error().decode())
+
+
+def _raise(L, rc: int) -> None:
+    if rc != TRAY_OK:
+        raise TrayError(rc, L.tray_last_error().decode())
+
+
+def accum_metric_params(lib_path: str | None = None, **overrides) -> AccumMetricParams:
+    """tray_accum_metric_default_params, with fields (tolerance, floor) overridden by name."""
+    p = AccumMetricParams()
+    L = lib(lib_path)
+    _raise(L, L.tray_accum_metric_default_params(ctypes.byref(p)))
+    for name, value in overrides.items():
+        if name not in dict(AccumMetricParams._fields_):
+            raise ValueError(f"unknown metric parameter {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def accum_fold_async(acc: Accum, frames_ptr: int | None, n_frames: int, device: int = 0, stream: int | None = None,
+                     lib_path: str | None = None) -> None:
+    """tray_accum_fold_async: folds n_frames device frames (rows x width x 3 f64 each, consecutive)
+    into acc's running mean and M2 in one launch; acc.count is updated. Only enqueues on `stream`."""
+    L = lib(lib_path)
+    _raise(L, L.tray_accum_fold_async(ctypes.byref(acc), frames_ptr, int(n_frames), int(device), stream))
+
+
+def accum_fold_metric_async(acc: Accum, frames_ptr: int | None, n_frames: int, metric_params: AccumMetricParams,
+                            variance_ptr: int | None = None, metric_ptr: int | None = None, device: int = 0,
+                            stream: int | None = None, lib_path: str | None = None) -> None:
+    """tray_accum_fold_metric_async: the fold with the variance of the mean (rows x width x 3 f64) and
+    the 16-byte convergence record (ACCUM_METRIC_DTYPE) of the state after it, in the same launch."""
+    L = lib(lib_path)
+    _raise(L, L.tray_accum_fold_metric_async(ctypes.byref(acc), frames_ptr, int(n_frames),
+                                             ctypes.byref(metric_params), variance_ptr, metric_ptr, int(device),
+                                             stream))
+
+
+def denoise_variance_params(width: int, rows: int, lib_path: str | None = None, **overrides) -> DenoiseVarianceParams:
+    """tray_denoise_variance_default_params for a width x rows image, with fields overridden by name."""
+    p = DenoiseVarianceParams()
+    L = lib(lib_path)
+    _raise(L, L.tray_denoise_variance_default_params(int(width), int(rows), ctypes.byref(p)))
+    for name, value in overrides.items():
+        if name not in dict(DenoiseVarianceParams._fields_):
+            raise ValueError(f"unknown variance-guided denoise parameter {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def denoise_variance_workspace_bytes(params: DenoiseVarianceParams, lib_path: str | None = None) -> int:
+    n = ctypes.c_size_t(0)
+    L = lib(lib_path)
+    _raise(L, L.tray_denoise_variance_workspace_bytes(ctypes.byref(params), ctypes.byref(n)))
+    return int(n.value)
+
+
+def denoise_variance_async(colour_ptr: int, variance_ptr: int, params: DenoiseVarianceParams, out_ptr: int,
+                           workspace_ptr: int | None, workspace_bytes: int, albedo_ptr: int | None = None,
+                           normal_ptr: int | None = None, depth_ptr: int | None = None,
+                           variance_out_ptr: int | None = None, device: int = 0, stream: int | None = None,
+                           lib_path: str | None = None) -> None:
+    """tray_denoise_variance_async: the a-trous filter with its colour bandwidth set per pixel from
+    the variance of the mean (rows x width x 3 f64); variance_out: rows x width f64, the last level's
+    noise plane. Only enqueues on `stream`."""
+    guides = DenoiseGuides(albedo_ptr, normal_ptr, depth_ptr)
+    L = lib(lib_path)
+    _raise(L, L.tray_denoise_variance_async(colour_ptr, variance_ptr, ctypes.byref(guides), ctypes.byref(params),
+                                            out_ptr, variance_out_ptr, workspace_ptr, int(workspace_bytes),
+                                            int(device), stream))
 
 
 def camera_rays_count(params: Params) -> int:

@@ -31,6 +31,7 @@
 #include <string>
 
 #include "../../include/tray_denoise.h"
+#include "../../include/tray_progressive.h"
 #include "tray_internal.hpp"
 
 namespace tray {
@@ -68,11 +69,11 @@ struct Tap {
     double c0, c1, c2, n0, n1, n2, z, u;
 };
 
-// One tap of the contract: the three edge-stopping terms, the weight, the sums.
-__device__ __forceinline__ void accumulate(const DenoiseLevel& L, double k, const Tap& p, const Tap& q, double& a0,
-                                           double& a1, double& a2, double& W) {
+// The weight of one tap of the contract: the three edge-stopping terms. q_c is the level's
+// constant (tray_denoise.h) or the pixel's r_i(p) (tray_progressive.h, section 3b).
+__device__ __forceinline__ double tap_weight(const DenoiseLevel& L, double q_c, double k, const Tap& p, const Tap& q) {
     const double d0 = p.c0 - q.c0, d1 = p.c1 - q.c1, d2 = p.c2 - q.c2;
-    const double x_c = ((d0 * d0 + d1 * d1) + d2 * d2) * L.q_c;
+    const double x_c = ((d0 * d0 + d1 * d1) + d2 * d2) * q_c;
     double w = k * edge_stop(x_c);
     if (L.normal) {
         const double e0 = p.n0 - q.n0, e1 = p.n1 - q.n1, e2 = p.n2 - q.n2;
@@ -84,6 +85,13 @@ __device__ __forceinline__ void accumulate(const DenoiseLevel& L, double k, cons
         const double x_z = (t * t) * L.q_z;
         w = w * edge_stop(x_z);
     }
+    return w;
+}
+
+// One tap of the contract: the weight, the sums.
+__device__ __forceinline__ void accumulate(const DenoiseLevel& L, double k, const Tap& p, const Tap& q, double& a0,
+                                           double& a1, double& a2, double& W) {
+    const double w = tap_weight(L, L.q_c, k, p, q);
     if (w > 0.0) {
         a0 = a0 + w * q.c0;
         a1 = a1 + w * q.c1;
@@ -140,8 +148,38 @@ __device__ __forceinline__ void store_pixel(const DenoiseLevel& L, size_t pix, c
 
 #ifndef TRAY_DENOISE_GLOBAL_TAPS
 
-__global__ __launch_bounds__(kThreads) void denoise_level_kernel(const DenoiseLevel L) {
-    __shared__ double lds[8][kLdsPoints];
+// What the variance-guided level (tray_progressive.h, section 3) has beyond DenoiseLevel.
+struct VarianceLevel {
+    const double* variance;  // level 0: rows x width x 3, the per-channel variance of the mean; else null
+    const double* plane_in;  // later levels: v_i, rows x width
+    double* plane_out;       // v_i+1; null when the last level's plane is not asked for
+    double S, epsilon;       // sigma_variance^2, epsilon
+};
+
+// v_0 of pixel `pix`: the scalar noise plane from the per-channel variance (in the units the
+// filter runs in: divided by m(albedo)^2 at the level that demodulates).
+__device__ __forceinline__ double noise_point(const DenoiseLevel& L, const VarianceLevel& V, size_t pix) {
+    if (!V.variance) return V.plane_in[pix];
+    double v0 = V.variance[3 * pix], v1 = V.variance[3 * pix + 1], v2 = V.variance[3 * pix + 2];
+    if (L.demodulate) {
+        const double m0 = albedo_floor(L.demodulate[3 * pix]), m1 = albedo_floor(L.demodulate[3 * pix + 1]),
+                     m2 = albedo_floor(L.demodulate[3 * pix + 2]);
+        v0 = v0 / (m0 * m0);
+        v1 = v1 / (m1 * m1);
+        v2 = v2 / (m2 * m2);
+    }
+    return (v0 + v1) + v2;
+}
+
+__device__ __forceinline__ double binomial_weight(int d) { return d == 0 ? 0.5 : 0.25; }  // h3 = (1/4, 1/2, 1/4)
+
+// One level for one workgroup. kVariance adds a ninth LDS plane, v_i (31,104 B: still 5
+// workgroups per CU). Its reads follow the other planes' pattern, a half-wave on 32 consecutive
+// doubles of one plane row at every tap and prefilter offset, and its staging stores are the
+// same k-indexed stores: no bank conflicts for the same reason.
+template <bool kVariance>
+__device__ __forceinline__ void denoise_level(const DenoiseLevel& L, const VarianceLevel& V) {
+    __shared__ double lds[kVariance ? 9 : 8][kLdsPoints];
     // Block -> (sub-image, tile). Uniform per block.
     uint32_t b = blockIdx.x;
     const int32_t tile_x = (int32_t)(b % (uint32_t)L.tiles_x);
@@ -160,7 +198,10 @@ __global__ __launch_bounds__(kThreads) void denoise_level_kernel(const DenoiseLe
         Tap t;
         t.c0 = nan;  // outside the image: skipped through b(NaN) = 0
         t.c1 = t.c2 = t.n0 = t.n1 = t.n2 = t.z = t.u = 0.0;
-        if (x >= 0 && x < L.width && y >= 0 && y < L.rows) t = load_point(L, (size_t)y * (size_t)L.width + (size_t)x);
+        const bool inside = x >= 0 && x < L.width && y >= 0 && y < L.rows;
+        if (inside) t = load_point(L, (size_t)y * (size_t)L.width + (size_t)x);
+        if constexpr (kVariance)
+            lds[8][k] = inside ? noise_point(L, V, (size_t)y * (size_t)L.width + (size_t)x) : 0.0;
         lds[0][k] = t.c0;
         lds[1][k] = t.c1;
         lds[2][k] = t.c2;
@@ -181,6 +222,23 @@ __global__ __launch_bounds__(kThreads) void denoise_level_kernel(const DenoiseLe
     p.n0 = lds[3][centre], p.n1 = lds[4][centre], p.n2 = lds[5][centre];
     p.z = lds[6][centre], p.u = lds[7][centre];
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, W = 0.0;
+    [[maybe_unused]] double r = 0.0, A = 0.0;
+    if constexpr (kVariance) {  // g_i(p): the 3 x 3 binomial mean of v_i over the in-image neighbours, then r_i(p)
+        double G = 0.0, B = 0.0;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int64_t qx = x + (int64_t)dx * L.s, qy = y + (int64_t)dy * L.s;
+                if (qx < 0 || qx >= L.width || qy < 0 || qy >= L.rows) continue;
+                const double k3 = binomial_weight(dy) * binomial_weight(dx);
+                G = G + k3 * lds[8][centre + dy * kLdsX + dx];
+                B = B + k3;
+            }
+        }
+        const double g = G / B;
+        r = 1.0 / (g > 0.0 ? V.S * g + V.epsilon : V.epsilon);
+    }
 #pragma unroll
     for (int dy = -2; dy <= 2; ++dy) {
 #pragma unroll
@@ -190,10 +248,35 @@ __global__ __launch_bounds__(kThreads) void denoise_level_kernel(const DenoiseLe
             q.c0 = lds[0][at], q.c1 = lds[1][at], q.c2 = lds[2][at];
             q.n0 = lds[3][at], q.n1 = lds[4][at], q.n2 = lds[5][at];
             q.z = lds[6][at], q.u = lds[7][at];
-            accumulate(L, kernel_weight(dy) * kernel_weight(dx), p, q, a0, a1, a2, W);
+            const double k = kernel_weight(dy) * kernel_weight(dx);
+            if constexpr (kVariance) {
+                const double w = tap_weight(L, r, k, p, q);
+                if (w > 0.0) {
+                    a0 = a0 + w * q.c0;
+                    a1 = a1 + w * q.c1;
+                    a2 = a2 + w * q.c2;
+                    W = W + w;
+                    A = A + (w * w) * lds[8][at];
+                }
+            } else {
+                accumulate(L, k, p, q, a0, a1, a2, W);
+            }
         }
     }
-    store_pixel(L, (size_t)y * (size_t)L.width + (size_t)x, p, a0, a1, a2, W);
+    const size_t pix = (size_t)y * (size_t)L.width + (size_t)x;
+    store_pixel(L, pix, p, a0, a1, a2, W);
+    if constexpr (kVariance) {
+        if (V.plane_out) V.plane_out[pix] = W > 0.0 ? A / (W * W) : lds[8][centre];
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void denoise_level_kernel(const DenoiseLevel L) {
+    denoise_level<false>(L, VarianceLevel{});
+}
+
+__global__ __launch_bounds__(kThreads) void denoise_variance_level_kernel(const DenoiseLevel L,
+                                                                          const VarianceLevel V) {
+    denoise_level<true>(L, V);
 }
 
 // Fills the tiling fields of L and returns the workgroups of its launch.
@@ -210,6 +293,13 @@ static hipError_t launch_level(DenoiseLevel& L, hipStream_t stream) {
     const int64_t blocks = plan_level(L);
     if (blocks > kMaxBlocks) return hipErrorInvalidConfiguration;  // tray_denoise_async refuses these first
     hipLaunchKernelGGL(denoise_level_kernel, dim3((uint32_t)blocks), dim3(kThreads), 0, stream, L);
+    return hipGetLastError();
+}
+
+static hipError_t launch_variance_level(DenoiseLevel& L, const VarianceLevel& V, hipStream_t stream) {
+    const int64_t blocks = plan_level(L);
+    if (blocks > kMaxBlocks) return hipErrorInvalidConfiguration;  // tray_denoise_variance_async refuses these first
+    hipLaunchKernelGGL(denoise_variance_level_kernel, dim3((uint32_t)blocks), dim3(kThreads), 0, stream, L, V);
     return hipGetLastError();
 }
 
@@ -266,6 +356,24 @@ bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
+
+#ifndef TRAY_DENOISE_GLOBAL_TAPS
+// tray_denoise_variance_params through the checks of tray_denoise_params (the shared fields), then its
+// own; the workspace holds a noise plane beside each intermediate image.
+int validate_variance(const tray_denoise_variance_params* p, int64_t* pixels, size_t* workspace) {
+    if (!p) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params");
+    const tray_denoise_params shared = {p->width, p->rows, p->iterations, p->flags, 1.0, p->sigma_normal,
+                                        p->sigma_depth};
+    const int rc = validate(&shared, pixels, workspace);
+    if (rc) return rc;
+    if (!(std::isfinite(p->sigma_variance) && p->sigma_variance > 0.0))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "sigma_variance must be finite and > 0");
+    if (!(std::isfinite(p->epsilon) && p->epsilon > 0.0))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "epsilon must be finite and > 0");
+    *workspace = *workspace / 3 * 4;
+    return TRAY_OK;
+}
+#endif
 
 }  // namespace
 }  // namespace tray
@@ -354,6 +462,107 @@ int tray_denoise_async(const double* colour, const tray_denoise_guides* guides, 
     }
     return TRAY_OK;
 }
+
+#ifndef TRAY_DENOISE_GLOBAL_TAPS  // include/tray_progressive.h, section 3
+
+int tray_denoise_variance_default_params(int32_t width, int32_t rows, tray_denoise_variance_params* out) {
+    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params (out)");
+    if (width < 0 || rows < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative width or rows");
+    out->width = width;
+    out->rows = rows;
+    out->iterations = 5;
+    out->flags = TRAY_DENOISE_DEMODULATE;
+    out->sigma_variance = 3.0;
+    out->sigma_normal = 0.5;
+    out->sigma_depth = 0.0625;
+    out->epsilon = 1e-12;
+    return TRAY_OK;
+}
+
+int tray_denoise_variance_workspace_bytes(const tray_denoise_variance_params* p, size_t* bytes) {
+    if (!bytes) return fail(TRAY_ERR_INVALID_ARGUMENT, "null bytes");
+    int64_t pixels = 0;
+    return validate_variance(p, &pixels, bytes);
+}
+
+int tray_denoise_variance_async(const double* colour, const double* variance, const tray_denoise_guides* guides,
+                                const tray_denoise_variance_params* p, double* out, double* variance_out,
+                                void* workspace, size_t workspace_bytes, int32_t device, void* stream) {
+    if (!colour) return fail(TRAY_ERR_INVALID_ARGUMENT, "null colour");
+    if (!variance) return fail(TRAY_ERR_INVALID_ARGUMENT, "null variance");
+    if (!guides) return fail(TRAY_ERR_INVALID_ARGUMENT, "null guides");
+    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null out");
+    int64_t pixels = 0;
+    size_t need = 0;
+    const int rc = validate_variance(p, &pixels, &need);
+    if (rc) return rc;
+    if ((p->flags & TRAY_DENOISE_DEMODULATE) && !guides->albedo)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "TRAY_DENOISE_DEMODULATE needs the albedo guide");
+    if (need && (!workspace || workspace_bytes < need))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "workspace smaller than tray_denoise_variance_workspace_bytes");
+    const size_t image_bytes = (size_t)pixels * 3 * sizeof(double), plane_bytes = (size_t)pixels * sizeof(double);
+    if (overlap(out, image_bytes, colour, image_bytes))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "out overlaps colour: the filter does not run in place");
+    if (overlap(out, image_bytes, variance, image_bytes)) return fail(TRAY_ERR_INVALID_ARGUMENT, "out overlaps variance");
+    if (need && overlap(out, image_bytes, workspace, need))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "out overlaps the workspace");
+    if (variance_out && (overlap(variance_out, plane_bytes, colour, image_bytes) ||
+                         overlap(variance_out, plane_bytes, variance, image_bytes) ||
+                         overlap(variance_out, plane_bytes, out, image_bytes) ||
+                         (need && overlap(variance_out, plane_bytes, workspace, need))))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "variance_out overlaps another buffer");
+    if (pixels == 0) return TRAY_OK;
+
+    const bool modulate = (p->flags & TRAY_DENOISE_DEMODULATE) != 0;
+    const size_t buffers = need / (image_bytes + plane_bytes);  // 0, 1 or 2
+    double* const base = static_cast<double*>(workspace);
+    double* const ping[2] = {base, base + (size_t)pixels * 3};
+    double* const planes[2] = {base + buffers * (size_t)pixels * 3, base + buffers * (size_t)pixels * 3 + (size_t)pixels};
+    DenoiseLevel L;
+    L.normal = guides->normal;
+    L.depth = guides->depth;
+    L.width = p->width;
+    L.rows = p->rows;
+    L.q_c = 0.0;  // not used: r_i(p) takes its place
+    L.q_n = 1.0 / (p->sigma_normal * p->sigma_normal);
+    L.q_z = 1.0 / (p->sigma_depth * p->sigma_depth);
+    L.tiles_x = L.tiles_y = L.lattices_x = 0;
+    for (int i = 0; i < p->iterations; ++i) {  // before any device work: all levels or none
+        L.s = 1 << i;
+        if (plan_level(L) > kMaxBlocks)
+            return fail(TRAY_ERR_TOO_LARGE, "a level of this image needs more than 2^24 - 1 workgroups");
+    }
+
+    int n_devices = 0;
+    if (hipGetDeviceCount(&n_devices) != hipSuccess || n_devices <= 0) return fail(TRAY_ERR_NO_DEVICE, "no device");
+    if (device < 0 || device >= n_devices) return fail(TRAY_ERR_INVALID_ARGUMENT, "no such device");
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail(TRAY_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    VarianceLevel V;
+    V.S = p->sigma_variance * p->sigma_variance;
+    V.epsilon = p->epsilon;
+    const double* in = colour;
+    const double* plane_in = nullptr;
+    for (int i = 0; i < p->iterations; ++i) {
+        const bool last = i == p->iterations - 1;
+        L.in = in;
+        L.out = last ? out : ping[i & 1];
+        L.demodulate = modulate && i == 0 ? guides->albedo : nullptr;
+        L.remodulate = modulate && last ? guides->albedo : nullptr;
+        L.s = 1 << i;
+        V.variance = i == 0 ? variance : nullptr;
+        V.plane_in = plane_in;
+        V.plane_out = last ? variance_out : planes[i & 1];
+        e = launch_variance_level(L, V, static_cast<hipStream_t>(stream));
+        if (e != hipSuccess)
+            return fail(TRAY_ERR_DEVICE, std::string("variance-guided denoise level: ") + hipGetErrorString(e));
+        in = L.out;
+        plane_in = V.plane_out;
+    }
+    return TRAY_OK;
+}
+
+#endif  // TRAY_DENOISE_GLOBAL_TAPS
 
 }  // extern "C"
 #pragma GCC visibility pop

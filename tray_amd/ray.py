@@ -553,6 +553,128 @@ class Tracer:  # ray/tracer.go:25-36
         self.imageData[:] = rgba.cpu().numpy()
         return self.imageData
 
+    def Accumulate(self, frames, tolerance: float | None = None, floor: float | None = None):
+        """The running mean of a stack of linear frames, (k, rows, W, 3) float64 (for instance k
+        progressive passes of the same pixels), and the per-channel variance of that mean
+        (include/tray_progressive.h, sections 1 and 2): two (rows, W, 3) float64 arrays, folded
+        on the device in one launch. The variance is +inf for k < 2. `unconverged` and
+        `max_ratio` receive the convergence record for `tolerance` and `floor` (the library's
+        defaults when None). Any rows of the image's width do. No Go counterpart."""
+        import torch
+
+        frames = np.ascontiguousarray(frames, dtype=np.float64)
+        if frames.ndim != 4 or frames.shape[2:] != (self.width, 3) or frames.shape[0] < 1:
+            raise ValueError(f"frames must be (k, rows, {self.width}, 3) with k >= 1; got {frames.shape}")
+        k, rows = frames.shape[:2]
+        overrides = {n: v for n, v in (("tolerance", tolerance), ("floor", floor)) if v is not None}
+        mp = _lib.accum_metric_params(**overrides)
+        if rows * self.width == 0:
+            self.unconverged, self.max_ratio = 0, 0.0
+            return frames[0].copy(), frames[0].copy()
+        device = int(self.Devices[0] if self.Devices else self.Device)
+        where = torch.device(f"cuda:{device}")
+        stack = torch.from_numpy(frames).to(where)
+        mean, m2, variance = (torch.empty((rows, self.width, 3), dtype=torch.float64, device=where) for _ in range(3))
+        record = torch.empty((2,), dtype=torch.float64, device=where)
+        acc = _lib.Accum(mean.data_ptr(), m2.data_ptr(), self.width, rows, 0, 0)
+        _lib.accum_fold_metric_async(acc, stack.data_ptr(), k, mp, variance.data_ptr(), record.data_ptr(), device,
+                                     torch.cuda.current_stream(where).cuda_stream)
+        rec = record.cpu().numpy().view(_lib.ACCUM_METRIC_DTYPE)[0]
+        self.unconverged, self.max_ratio = int(rec["unconverged"]), float(rec["max_ratio"])
+        return mean.cpu().numpy(), variance.cpu().numpy()
+
+    def RenderProgressive(self, scene: Scene | None, max_passes: int, batch: int = 4, tolerance: float | None = None,
+                          denoise: bool = False, guides: dict | None = None, fraction: float = 0.0,
+                          floor: float | None = None, **overrides) -> np.ndarray:
+        """Keeps rendering until the picture is good enough: progressive passes of
+        NumRaysPerPixel samples each (tray_render_passes_async, `batch` passes per launch into one
+        device buffer), folded into a running mean with the variance of that mean and the
+        convergence record (tray_accum_fold_metric_async), and a 16-byte readback per batch. It
+        stops when at most `fraction` of the pixels are unconverged at `tolerance` (the relative
+        standard error; the library's default when None; never before 2 passes, whose variance is
+        the first there is), or after max_passes. The seed is drawn once for the whole call and
+        kept in `seed`, so the passes are one random stream also with Seed = 0. Everything is
+        enqueued on one stream and no frame leaves the device before the end.
+
+        With denoise=True the mean goes through the variance-guided filter
+        (tray_denoise_variance_async; overrides: fields of tray_denoise_variance_params), guided by
+        `guides` (a dict of albedo, normal, depth arrays as RenderAOV returns) or, when None, by the
+        feature buffers of the first pass (tray_render_aov_async). Returns (H, W, 4) uint8 RGBA
+        (tray_linear_to_srgba_async) like Render and keeps it in imageData; `linear` holds the FP64
+        frame shown, `variance` the per-channel variance of the mean, `passes` the passes done,
+        `unconverged` and `max_ratio` the last record. No Go counterpart."""
+        import torch
+
+        if max_passes < 1 or batch < 1:
+            raise ValueError("max_passes and batch must be >= 1")
+        if overrides and not denoise:
+            raise ValueError(f"filter parameters {sorted(overrides)} given without denoise=True")
+        scene = self._apply_defaults(scene)
+        self.Camera.Initialize(self.width, self.height)
+        device = int(self.Devices[0] if self.Devices else self.Device)
+        where = torch.device(f"cuda:{device}")
+        self.seed = self._seed()  # once: every pass draws from this stream
+        mp = _lib.accum_metric_params(**{n: v for n, v in (("tolerance", tolerance), ("floor", floor))
+                                         if v is not None})
+        h, w = self.height, self.width
+        self.passes, self.unconverged, self.max_ratio = 0, h * w, 0.0
+        self.variance = np.full((h, w, 3), np.inf)
+        if h * w == 0:
+            return self.imageData
+        stream = torch.cuda.current_stream(where).cuda_stream
+        dev = scene._device_scene(device)
+        f64 = dict(dtype=torch.float64, device=where)
+        frames = torch.empty((min(batch, max_passes), h, w, 3), **f64)
+        mean, m2, variance = (torch.empty((h, w, 3), **f64) for _ in range(3))
+        record = torch.empty((2,), **f64)
+        acc = _lib.Accum(mean.data_ptr(), m2.data_ptr(), w, h, 0, 0)
+        aov = None
+        if denoise:
+            if guides is None:
+                aov = {name: torch.empty((h, w, 3)[: 3 if ch > 1 else 2], **f64)
+                       for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1))}
+                p0 = _lib.make_params(w, h, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, self.seed, 0, h)
+                dev.render_aov_async(self.Camera._state, p0, aov["albedo"].data_ptr(), aov["normal"].data_ptr(),
+                                     aov["depth"].data_ptr(), stream=stream)
+            else:
+                aov = {}
+                for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1)):
+                    g = guides.get(name)
+                    if g is None:
+                        continue
+                    g = np.ascontiguousarray(g, dtype=np.float64)
+                    if g.shape != (h, w) + ((3,) if ch == 3 else ()):
+                        raise ValueError(f"{name} must cover the frame; got {g.shape}")
+                    aov[name] = torch.from_numpy(g).to(where)
+        while self.passes < max_passes:
+            n = min(batch, max_passes - self.passes)
+            params = _lib.make_params(w, h, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, self.seed, 0, h,
+                                      pass_=self.passes)
+            dev.render_passes_async(self.Camera._state, params, n, frames.data_ptr(), stream)
+            _lib.accum_fold_metric_async(acc, frames.data_ptr(), n, mp, variance.data_ptr(), record.data_ptr(),
+                                         device, stream)
+            rec = record.cpu().numpy().view(_lib.ACCUM_METRIC_DTYPE)[0]  # the 16-byte readback
+            self.passes = int(acc.count)
+            self.unconverged, self.max_ratio = int(rec["unconverged"]), float(rec["max_ratio"])
+            if self.passes >= 2 and self.unconverged <= fraction * (h * w):
+                break
+        shown = mean
+        if denoise:
+            dp = _lib.denoise_variance_params(w, h, **overrides)
+            nbytes = _lib.denoise_variance_workspace_bytes(dp)
+            shown = torch.empty_like(mean)
+            work = torch.empty((max(nbytes, 8) // 8,), **f64)
+            _lib.denoise_variance_async(mean.data_ptr(), variance.data_ptr(), dp, shown.data_ptr(),
+                                        work.data_ptr() if nbytes else None, nbytes,
+                                        *(aov[k].data_ptr() if aov.get(k) is not None else None
+                                          for k in ("albedo", "normal", "depth")), device=device, stream=stream)
+        rgba = torch.empty((h, w, 4), dtype=torch.uint8, device=where)
+        _lib.linear_to_srgba_async(shown.data_ptr(), h * w, rgba.data_ptr(), device, stream)
+        self.linear[:] = shown.cpu().numpy()
+        self.variance = variance.cpu().numpy()
+        self.imageData[:] = rgba.cpu().numpy()
+        return self.imageData
+
     def RenderLines(self, idx: int, yStart: int, yEnd: int, scene: Scene) -> None:  # ray/tracer.go:120-155
         """Render rows [yStart, yEnd) with the current (initialized) camera and
         fields; like Go, no defaulting happens here."""
