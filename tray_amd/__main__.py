@@ -8,6 +8,8 @@ have no meaning here).
     python -m tray_amd -denoise -r 16 ... # the frame filtered on the device (include/tray_denoise.h)
     python -m tray_amd -r 16 -passes 64 [-tolerance T] [-denoise] ...  # progressive: passes of -r rays until
                                           # the frame has converged (include/tray_progressive.h)
+    python -m tray_amd -r 16 -passes 64 -adaptive [-denoise] ...  # the same, rendering only the pixels
+                                          # that have not converged yet (include/tray_adaptive.h)
 """
 from __future__ import annotations
 
@@ -56,6 +58,9 @@ def main(argv=None) -> int:
     ap.add_argument("-tolerance", type=float, default=None, metavar="T",
                     help="with -passes: the relative standard error at which a pixel counts as converged "
                          "(default: the library's, 0.05)")
+    ap.add_argument("-adaptive", action="store_true",
+                    help="with -passes: render only the unconverged pixels after a uniform warm-up "
+                         "(include/tray_adaptive.h); prints the pixel-passes spent against h x w x passes")
     ap.add_argument("-ansi", action="store_true",
                     help="render at -s x the terminal size and draw it in the terminal (main.go:86-131)")
     ap.add_argument("-s", type=float, default=4, help="supersampling factor of -ansi")
@@ -67,16 +72,25 @@ def main(argv=None) -> int:
     t.NumRaysPerPixel, t.MaxDepth, t.Seed = a.r, a.d, a.seed
     scene = ray.RichScene(a.seed)
     t0 = time.perf_counter()
-    if a.passes > 0:
+    samples = a.width * a.height * a.r
+    if a.adaptive:
+        if a.passes <= 0:
+            ap.error("-adaptive needs -passes N")
+        img = t.RenderAdaptive(scene, a.passes, tolerance=a.tolerance, denoise=a.denoise)
+        samples *= t.pixel_passes / max(a.width * a.height, 1)
+        print(f"adaptive: {t.pixel_passes} pixel-passes of r={a.r} against {a.width * a.height * a.passes} "
+              f"(h x w x passes), at most {t.passes} in a pixel, {t.unconverged} of {a.width * a.height} pixels "
+              f"unconverged, worst relative error {t.max_ratio ** 0.5:.4g}")
+    elif a.passes > 0:
         img = t.RenderProgressive(scene, a.passes, tolerance=a.tolerance, denoise=a.denoise)
         print(f"progressive: {t.passes} passes of r={a.r} done, {t.unconverged} of {a.width * a.height} pixels "
               f"unconverged, worst relative error {t.max_ratio ** 0.5:.4g}")
+        samples *= t.passes
     else:
         img = t.RenderDenoised(scene) if a.denoise else t.Render(scene)
     dt = time.perf_counter() - t0
     print(f"rendered {a.width}x{a.height} r={a.r} d={a.d}{' denoised' if a.denoise else ''} "
-          f"({len(scene.Objects)} objects) in {dt:.3f} s: "
-          f"{a.width * a.height * a.r * max(a.passes and t.passes, 1) / dt / 1e6:.1f} Mrays/s end to end",
+          f"({len(scene.Objects)} objects) in {dt:.3f} s: {samples / dt / 1e6:.1f} Mrays/s end to end",
           file=sys.stderr)
     if a.save:
         png.save_png(a.save, img)

@@ -293,6 +293,42 @@ class DenoiseVarianceParams(ctypes.Structure):
 assert ctypes.sizeof(Accum) == 32 and ctypes.sizeof(AccumMetricParams) == 16 and ctypes.sizeof(AccumMetric) == 16
 assert ctypes.sizeof(DenoiseVarianceParams) == 48 and ACCUM_METRIC_DTYPE.itemsize == 16
 
+# Every symbol include/tray_adaptive.h declares (the renderer over a pixel list, the fold with
+# per-pixel counts and the selection step; in none of the six lists above).
+ADAPTIVE_EXPORTS = (
+    "tray_adaptive_version",
+    "tray_adaptive_default_params",
+    "tray_render_pixels_async",
+    "tray_adaptive_fold_async",
+    "tray_adaptive_workspace_bytes",
+    "tray_adaptive_select_async",
+)
+
+
+class AdaptiveState(ctypes.Structure):
+    """tray_adaptive_state: the device state (mean, m2, count) of a width x rows image."""
+    _fields_ = [("mean", ctypes.c_void_p), ("m2", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("width", ctypes.c_int32), ("rows", ctypes.c_int32)]
+
+
+class AdaptiveParams(ctypes.Structure):
+    """tray_adaptive_params."""
+    _fields_ = [("tolerance", ctypes.c_double), ("floor", ctypes.c_double), ("min_passes", ctypes.c_int32),
+                ("max_passes", ctypes.c_int32), ("dilate", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class AdaptiveRecord(ctypes.Structure):
+    """tray_adaptive_record: the 32-byte device record."""
+    _fields_ = [("n_active", ctypes.c_uint64), ("unconverged", ctypes.c_uint64), ("max_ratio", ctypes.c_double),
+                ("pixel_passes", ctypes.c_uint64)]
+
+
+# tray_adaptive_record as a numpy structured dtype, for reading the record back.
+ADAPTIVE_RECORD_DTYPE = np.dtype([("n_active", "<u8"), ("unconverged", "<u8"), ("max_ratio", "<f8"),
+                                  ("pixel_passes", "<u8")])
+assert ctypes.sizeof(AdaptiveState) == 32 and ctypes.sizeof(AdaptiveParams) == 32
+assert ctypes.sizeof(AdaptiveRecord) == 32 and ADAPTIVE_RECORD_DTYPE.itemsize == 32
+
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
 DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear", "tray_debug_progress_counts")
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
@@ -405,6 +441,15 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.tray_denoise_variance_async.argtypes = [vp, vp, ctypes.POINTER(DenoiseGuides),
                                                   ctypes.POINTER(DenoiseVarianceParams), vp, vp, vp, ctypes.c_size_t,
                                                   i32, vp]
+    if hasattr(L, "tray_adaptive_version"):  # include/tray_adaptive.h; absent from older builds (A/B tools)
+        L.tray_adaptive_version.restype = i32
+        L.tray_adaptive_default_params.argtypes = [ctypes.POINTER(AdaptiveParams)]
+        L.tray_render_pixels_async.argtypes = [vp, ctypes.POINTER(CameraState), ctypes.POINTER(Params), vp,
+                                               ctypes.c_int64, vp, i32, vp, vp, vp]
+        L.tray_adaptive_fold_async.argtypes = [ctypes.POINTER(AdaptiveState), vp, ctypes.c_int64, vp, i32, i32, vp]
+        L.tray_adaptive_workspace_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+        L.tray_adaptive_select_async.argtypes = [ctypes.POINTER(AdaptiveState), ctypes.POINTER(AdaptiveParams), vp, vp,
+                                                 vp, vp, ctypes.c_size_t, i32, vp]
     if hasattr(L, "tray_debug_set"):  # absent from older builds (A/B tools)
         L.tray_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
         L.tray_debug_clear.argtypes = [ctypes.c_char_p]
@@ -734,6 +779,46 @@ def denoise_variance_async(colour_ptr: int, variance_ptr: int, params: DenoiseVa
                                             int(device), stream))
 
 
+def adaptive_params(lib_path: str | None = None, **overrides) -> AdaptiveParams:
+    """tray_adaptive_default_params, with fields overridden by name."""
+    p = AdaptiveParams()
+    L = lib(lib_path)
+    _raise(L, L.tray_adaptive_default_params(ctypes.byref(p)))
+    for name, value in overrides.items():
+        if name not in dict(AdaptiveParams._fields_):
+            raise ValueError(f"unknown adaptive parameter {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def adaptive_workspace_bytes(width: int, rows: int, lib_path: str | None = None) -> int:
+    n = ctypes.c_size_t(0)
+    L = lib(lib_path)
+    _raise(L, L.tray_adaptive_workspace_bytes(int(width), int(rows), ctypes.byref(n)))
+    return int(n.value)
+
+
+def adaptive_fold_async(state: AdaptiveState, pixels_ptr: int | None, n_pixels: int, values_ptr: int | None,
+                        n_passes: int, device: int = 0, stream: int | None = None,
+                        lib_path: str | None = None) -> None:
+    """tray_adaptive_fold_async: folds n_passes values (n_passes x n_pixels x 3 f64, pass-major) of the
+    listed (distinct) compact pixels into the state, each at its own count. Only enqueues on `stream`."""
+    L = lib(lib_path)
+    _raise(L, L.tray_adaptive_fold_async(ctypes.byref(state), pixels_ptr, int(n_pixels), values_ptr, int(n_passes),
+                                         int(device), stream))
+
+
+def adaptive_select_async(state: AdaptiveState, params: AdaptiveParams, pixels_ptr: int, record_ptr: int,
+                          workspace_ptr: int | None, workspace_bytes: int, variance_ptr: int | None = None,
+                          device: int = 0, stream: int | None = None, lib_path: str | None = None) -> None:
+    """tray_adaptive_select_async: the per-pixel metric, the dilation and the ascending list of the
+    active pixels (rows x width u32), with the 32-byte record (ADAPTIVE_RECORD_DTYPE) and, when
+    asked for, the variance of the mean (rows x width x 3 f64). Only enqueues on `stream`."""
+    L = lib(lib_path)
+    _raise(L, L.tray_adaptive_select_async(ctypes.byref(state), ctypes.byref(params), variance_ptr, pixels_ptr,
+                                           record_ptr, workspace_ptr, int(workspace_bytes), int(device), stream))
+
+
 def camera_rays_count(params: Params) -> int:
     """Rays tray_camera_rays_async writes for `params`: rows x width x rays_per_pixel."""
     return params_rows(params) * params.width * params.rays_per_pixel
@@ -837,6 +922,18 @@ class DeviceScene:
         out = AovBuffers(albedo_ptr, normal_ptr, depth_ptr, coverage_ptr, index_ptr)
         rc = self.L.tray_render_aov_async(self.handle, ctypes.byref(camera), ctypes.byref(params), ctypes.byref(out),
                                           stream)
+        if rc != TRAY_OK:
+            raise TrayError(rc, self.L.tray_last_error().decode())
+
+    def render_pixels_async(self, camera: CameraState, params: Params, pixels_ptr: int | None, n_pixels: int,
+                            out_ptr: int | None, n_passes: int = 1, pass_plane_ptr: int | None = None,
+                            segments_ptr: int | None = None, stream: int | None = None) -> None:
+        """tray_render_pixels_async: the ordered-sum means of n_pixels listed compact pixels (u32) of
+        params' row set, passes params.pass_ + plane[pixel] + k for k < n_passes, into out
+        (n_passes x n_pixels x 3 f64; segments: n_passes x n_pixels u32)."""
+        rc = self.L.tray_render_pixels_async(self.handle, ctypes.byref(camera), ctypes.byref(params), pixels_ptr,
+                                             int(n_pixels), pass_plane_ptr, int(n_passes), out_ptr, segments_ptr,
+                                             stream)
         if rc != TRAY_OK:
             raise TrayError(rc, self.L.tray_last_error().decode())
 

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/tray.h"
+#include "../../include/tray_adaptive.h"
 #include "../../include/tray_debug.h"
 #include "tray_internal.hpp"
 #include "bvh.hpp"
@@ -1065,6 +1066,54 @@ int tray_render_aov_async(tray_scene_t sc, const tray_camera* cam, const tray_pa
     TRAY_HIP(hipSetDevice(sc->device));
     TRAY_HIP(launch_render_aov(k, sc->has_bvh && !(p->flags & TRAY_FLAG_LINEAR_SCAN), sc->bvh_bound, *out,
                                static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
+// ---- the renderer over a pixel list (include/tray_adaptive.h, section 2) ---------
+int tray_render_pixels_async(tray_scene_t sc, const tray_camera* cam, const tray_params* p,
+                             const uint32_t* pixels_device, int64_t n_pixels, const int32_t* pass_plane_device,
+                             int32_t n_passes, double* out_device, uint32_t* segments_device, void* stream) {
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
+    int rc = validate_params(p);
+    if (rc) return rc;
+    if (p->output != TRAY_OUT_RGB_F64)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "a pixel list renders TRAY_OUT_RGB_F64 only");
+    if (n_pixels < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative n_pixels");
+    if (n_passes < 1) return fail(TRAY_ERR_INVALID_ARGUMENT, "n_passes must be >= 1");
+    if (((uint64_t)p->pass + (uint64_t)n_passes) * (uint64_t)p->rays_per_pixel > 0x100000000ull)
+        return fail(TRAY_ERR_TOO_LARGE, "(pass + n_passes) x rays_per_pixel exceeds the 32-bit RNG sample word");
+    const int64_t rows = tray_params_rows(p);
+    if (rows * (int64_t)p->width > kQueryMaxRays)
+        return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one row set");
+    // n_pixels x n_passes x r <= 2^31 - 1, without overflow: each factor is below 2^63 / 2^31.
+    if (n_pixels > kQueryMaxRays || n_pixels * (int64_t)n_passes > kQueryMaxRays ||
+        n_pixels * (int64_t)n_passes > kQueryMaxRays / p->rays_per_pixel)
+        return fail(TRAY_ERR_TOO_LARGE, "n_pixels x n_passes x rays_per_pixel exceeds 2^31 - 1");
+    if (n_pixels == 0) return TRAY_OK;
+    if (!pixels_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null pixel list");
+    if (!out_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null result buffer");
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    k.width = p->width;
+    k.height = p->height;
+    k.spp = p->rays_per_pixel;
+    k.max_depth = p->max_depth;
+    k.y_start = p->y_start;
+    k.rows = (int32_t)rows;
+    k.tile_rows = p->tile_rows;
+    k.tile_count = p->tile_rows > 0 ? p->tile_count : 1;
+    k.tile_index = p->tile_rows > 0 ? p->tile_index : 0;
+    k.ray_radius = p->ray_radius;
+    k.passes = (uint32_t)n_passes;
+    k.pass0 = (uint32_t)p->pass;
+    camera_params(cam, k);
+    key_params(p->seed, k);
+    TRAY_HIP(hipSetDevice(sc->device));
+    TRAY_HIP(launch_render_pixels(k, sc->has_bvh && !(p->flags & TRAY_FLAG_LINEAR_SCAN), sc->bvh_bound, pixels_device,
+                                  (uint32_t)n_pixels, pass_plane_device, (uint32_t)n_passes, out_device,
+                                  segments_device, static_cast<hipStream_t>(stream)));
     return TRAY_OK;
 }
 

@@ -164,6 +164,27 @@ __device__ __forceinline__ QStack lane_stack() {
     return QStack{(__attribute__((address_space(3))) uint32_t*)query_stacks + threadIdx.x};
 }
 
+// The stacks of one workgroup; the dynamic-LDS default limit (64 KB) bounds them.
+static size_t query_stack_bytes(int32_t stack_cap) { return (size_t)stack_cap * kQueryBlock * sizeof(uint32_t); }
+constexpr size_t kQueryLdsMax = 64 * 1024;
+
+static QueryArgs query_args(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays, uint32_t n,
+                            size_t& lds) {
+    QueryArgs q{};
+    q.rays = rays;
+    q.n = n;
+    lds = query_stack_bytes(p.stack_cap);
+    q.use_bvh = use_bvh && p.n_nodes > 0 && lds <= kQueryLdsMax ? 1 : 0;
+    if (!q.use_bvh) lds = 0;
+    q.bound = bound;
+    q.t_end = __builtin_inf();
+    return q;
+}
+
+// With TRAY_QUERY_DEVICE_FUNCTIONS_ONLY the query kernels and their launchers are left
+// out: tray_adaptive.hip includes this file for the functions above and for scatter_step
+// and query_shade below, as this file includes tray_kernel.hip.
+#ifndef TRAY_QUERY_DEVICE_FUNCTIONS_ONLY
 // Camera.GetRay: lane i is sample s of pixel (x, compact row j), i = (j * width + x) * r + s.
 __global__ __launch_bounds__(256) void camera_rays_kernel(KernelParams p, tray_ray* rays, uint32_t* ids, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -217,6 +238,7 @@ __global__ __launch_bounds__(kQueryBlock) void scene_hit_kernel(KernelParams p, 
     o->index = h.tree ? sv.bidx[h.ref] : h.ref;
     o->front_face = front ? 1 : 0;
 }
+#endif  // TRAY_QUERY_DEVICE_FUNCTIONS_ONLY
 
 // Material.Scatter (ray/materials.go:13-64) of a ray with direction `dir` (a = |dir|^2) at a
 // hit whose record has `normal` and `front`: the draws of (pixel, sample, bounce, purpose 3),
@@ -300,6 +322,7 @@ __device__ __forceinline__ bool query_shade(const KernelParams& p, const SceneVi
     return true;
 }
 
+#ifndef TRAY_QUERY_DEVICE_FUNCTIONS_ONLY
 // Scene.RayColor: one path per lane, the recursion as the megakernel's bounce loop.
 // Segments count the path's Scene.Hit calls. Five waves per SIMD: the budget of 96 VGPRs
 // costs no scratch and fewer scalar spills than the compiler's own 98 at four waves, and
@@ -466,28 +489,11 @@ __global__ __launch_bounds__(kQueryBlock) void aov_kernel(KernelParams p, QueryA
     if (a.out.index) a.out.index[i] = first;
 }
 
-// The stacks of one workgroup; the dynamic-LDS default limit (64 KB) bounds them.
-static size_t query_stack_bytes(int32_t stack_cap) { return (size_t)stack_cap * kQueryBlock * sizeof(uint32_t); }
-constexpr size_t kQueryLdsMax = 64 * 1024;
-
 hipError_t launch_camera_rays(KernelParams p, tray_ray* rays, uint32_t* ids, uint32_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     p.div_tile_rows = make_fastdiv((uint32_t)std::max(p.tile_rows, 1));  // row_of
     hipLaunchKernelGGL(camera_rays_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, p, rays, ids, n);
     return hipGetLastError();
-}
-
-static QueryArgs query_args(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays, uint32_t n,
-                            size_t& lds) {
-    QueryArgs q{};
-    q.rays = rays;
-    q.n = n;
-    lds = query_stack_bytes(p.stack_cap);
-    q.use_bvh = use_bvh && p.n_nodes > 0 && lds <= kQueryLdsMax ? 1 : 0;
-    if (!q.use_bvh) lds = 0;
-    q.bound = bound;
-    q.t_end = __builtin_inf();
-    return q;
 }
 
 hipError_t launch_scene_hit(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays, uint32_t n,
@@ -562,5 +568,6 @@ hipError_t launch_render_aov(KernelParams p, bool use_bvh, double bound, const t
                        p, q, a);
     return hipGetLastError();
 }
+#endif  // TRAY_QUERY_DEVICE_FUNCTIONS_ONLY
 
 }  // namespace tray

@@ -54,4 +54,13 @@ hipError_t launch_scene_occluded(const KernelParams& p, bool use_bvh, double bou
 hipError_t launch_render_aov(KernelParams p, bool use_bvh, double bound, const tray_aov_buffers& out,
                              hipStream_t stream);
 
+// include/tray_adaptive.h section 2 (tray_adaptive.hip).
+// The ordered-sum pixel means of n_pixels listed compact pixels of p's row set, passes
+// p.pass0 + pass_plane[pixel] + k for k < n_passes, p.spp samples each: p's scene, camera,
+// image, row-set and draw-key fields. n_pixels x n_passes x p.spp <= 2^31 - 1. use_bvh and
+// bound as for launch_scene_hit; pass_plane and segments nullable.
+hipError_t launch_render_pixels(KernelParams p, bool use_bvh, double bound, const uint32_t* pixels, uint32_t n_pixels,
+                                const int32_t* pass_plane, uint32_t n_passes, double* out, uint32_t* segments,
+                                hipStream_t stream);
+
 }  // namespace tray

@@ -675,6 +675,155 @@ class Tracer:  # ray/tracer.go:25-36
         self.imageData[:] = rgba.cpu().numpy()
         return self.imageData
 
+    def RenderPixels(self, scene: Scene | None, pixels, passes: int = 1, pass_: int = 0) -> np.ndarray:
+        """The linear FP64 colour of the listed pixels alone (tray_render_pixels_async): `pixels` holds
+        n indices y * width + x of the frame Render(scene) draws, with Render's defaulting; returns
+        (passes, n, 3) float64, progressive passes pass_ .. pass_ + passes - 1. Each value has the
+        bits of that pixel in an ordered-sum render of that pass (TRAY_FLAG_ORDERED_SUM), whichever
+        other pixels are listed; an index outside the image gets zeros. For a region of interest or
+        for rendering a picked pixel again. Set Seed for values that repeat. No Go counterpart."""
+        import torch
+
+        if passes < 1:
+            raise ValueError("passes must be >= 1")
+        idx = np.ascontiguousarray(pixels)
+        if idx.ndim != 1 or (idx.size and (idx.dtype.kind not in "iu" or idx.min() < 0 or idx.max() >= 2 ** 32)):
+            raise ValueError("pixels must be a 1-d array of indices y * width + x in [0, 2^32)")
+        idx = idx.astype(np.uint32)
+        scene = self._apply_defaults(scene)
+        self.Camera.Initialize(self.width, self.height)
+        device = int(self.Devices[0] if self.Devices else self.Device)
+        where = torch.device(f"cuda:{device}")
+        params = _lib.make_params(self.width, self.height, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius,
+                                  self._seed(), 0, self.height, pass_=pass_)
+        n = int(idx.size)
+        out = torch.empty((passes, n, 3), dtype=torch.float64, device=where)
+        lst = torch.from_numpy(idx.view(np.int32)).to(where)
+        scene._device_scene(device).render_pixels_async(
+            self.Camera._state, params, lst.data_ptr() if n else None, n, out.data_ptr() if n else None, passes,
+            stream=torch.cuda.current_stream(where).cuda_stream)
+        return out.cpu().numpy()
+
+    def RenderAdaptive(self, scene: Scene | None, max_passes: int, min_passes: int | None = None, batch: int = 4,
+                       tolerance: float | None = None, floor: float | None = None, dilate: int = 1,
+                       denoise: bool = False, guides: dict | None = None, **overrides) -> np.ndarray:
+        """RenderProgressive that spends its samples where the picture is still noisy
+        (include/tray_adaptive.h). A warm-up of min_passes uniform passes through the megakernel
+        (tray_render_passes_async with the ordered sum, folded by tray_accum_fold_async; the
+        library's default when None); then rounds of tray_adaptive_select_async (the per-pixel
+        metric, widened by one pixel when `dilate`, compacted into a list), a 32-byte readback,
+        tray_render_pixels_async over that list (`batch` more passes of each listed pixel, numbered
+        from the pixel's own count) and tray_adaptive_fold_async, all on one stream. It stops when no
+        pixel is active: every pixel is converged at `tolerance` or has max_passes. A pixel's k-th
+        pass is the same whether it is rendered with the whole frame or in a list, so every pixel's
+        (mean, m2) is the uniform ordered-sum state after `counts` passes. The seed is drawn once
+        and kept in `seed`.
+
+        denoise, guides and overrides as for RenderProgressive. Returns (H, W, 4) uint8 RGBA and
+        keeps it in imageData; `linear` holds the FP64 frame shown, `variance` the per-channel
+        variance of the mean, `counts` the (H, W) int32 passes of each pixel, `passes` their maximum,
+        `pixel_passes` their sum, `unconverged` and `max_ratio` the last record. No Go counterpart."""
+        import torch
+
+        if max_passes < 1 or batch < 1:
+            raise ValueError("max_passes and batch must be >= 1")
+        if overrides and not denoise:
+            raise ValueError(f"filter parameters {sorted(overrides)} given without denoise=True")
+        given = {n: v for n, v in (("tolerance", tolerance), ("floor", floor)) if v is not None}
+        ap = _lib.adaptive_params(max_passes=int(max_passes), dilate=int(dilate), **given)
+        ap.min_passes = min(int(min_passes) if min_passes is not None else ap.min_passes, int(max_passes))
+        if ap.min_passes < 1:
+            raise ValueError("min_passes must be >= 1")
+        scene = self._apply_defaults(scene)
+        self.Camera.Initialize(self.width, self.height)
+        device = int(self.Devices[0] if self.Devices else self.Device)
+        where = torch.device(f"cuda:{device}")
+        self.seed = self._seed()  # once: every pass draws from this stream
+        h, w = self.height, self.width
+        self.passes, self.pixel_passes, self.unconverged, self.max_ratio = 0, 0, h * w, 0.0
+        self.variance = np.full((h, w, 3), np.inf)
+        self.counts = np.zeros((h, w), dtype=np.int32)
+        if h * w == 0:
+            return self.imageData
+        stream = torch.cuda.current_stream(where).cuda_stream
+        dev = scene._device_scene(device)
+        f64 = dict(dtype=torch.float64, device=where)
+
+        def make_params(pass_=0, flags=0):
+            return _lib.make_params(w, h, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, self.seed, 0, h,
+                                    flags=flags, pass_=pass_)
+
+        mean, m2, variance = (torch.empty((h, w, 3), **f64) for _ in range(3))
+        counts = torch.full((h, w), ap.min_passes, dtype=torch.int32, device=where)
+        aov = None
+        if denoise:
+            if guides is None:
+                aov = {name: torch.empty((h, w, 3)[: 3 if ch > 1 else 2], **f64)
+                       for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1))}
+                dev.render_aov_async(self.Camera._state, make_params(), aov["albedo"].data_ptr(),
+                                     aov["normal"].data_ptr(), aov["depth"].data_ptr(), stream=stream)
+            else:
+                aov = {}
+                for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1)):
+                    g = guides.get(name)
+                    if g is None:
+                        continue
+                    g = np.ascontiguousarray(g, dtype=np.float64)
+                    if g.shape != (h, w) + ((3,) if ch == 3 else ()):
+                        raise ValueError(f"{name} must cover the frame; got {g.shape}")
+                    aov[name] = torch.from_numpy(g).to(where)
+        # The warm-up: uniform passes through the megakernel, in launches of at most `batch`.
+        frames = torch.empty((min(batch, ap.min_passes), h, w, 3), **f64)
+        acc = _lib.Accum(mean.data_ptr(), m2.data_ptr(), w, h, 0, 0)
+        while acc.count < ap.min_passes:
+            n = min(batch, ap.min_passes - acc.count)
+            dev.render_passes_async(self.Camera._state, make_params(acc.count, _lib.FLAG_ORDERED_SUM), n,
+                                    frames.data_ptr(), stream)
+            _lib.accum_fold_async(acc, frames.data_ptr(), n, device, stream)
+        del frames
+        state = _lib.AdaptiveState(mean.data_ptr(), m2.data_ptr(), counts.data_ptr(), w, h)
+        nbytes = _lib.adaptive_workspace_bytes(w, h)
+        work = torch.empty((nbytes // 8,), **f64)
+        active = torch.empty((h * w,), dtype=torch.int32, device=where)
+        record = torch.empty((4,), **f64)
+        values = None
+
+        def select():
+            _lib.adaptive_select_async(state, ap, active.data_ptr(), record.data_ptr(), work.data_ptr(), nbytes,
+                                       variance.data_ptr(), device, stream)
+            return record.cpu().numpy().view(_lib.ADAPTIVE_RECORD_DTYPE)[0]  # the 32-byte readback
+
+        while True:
+            rec = select()
+            n_active = int(rec["n_active"])
+            if n_active == 0:
+                break
+            if values is None or values.shape[1] < n_active:  # the lists only shrink between rounds, almost
+                values = torch.empty((batch, n_active, 3), **f64)
+            dev.render_pixels_async(self.Camera._state, make_params(), active.data_ptr(), n_active, values.data_ptr(),
+                                    batch, pass_plane_ptr=counts.data_ptr(), stream=stream)
+            _lib.adaptive_fold_async(state, active.data_ptr(), n_active, values.data_ptr(), batch, device, stream)
+        self.unconverged, self.max_ratio = int(rec["unconverged"]), float(rec["max_ratio"])
+        self.pixel_passes = int(rec["pixel_passes"])
+        shown = mean
+        if denoise:
+            dp = _lib.denoise_variance_params(w, h, **overrides)
+            dbytes = _lib.denoise_variance_workspace_bytes(dp)
+            shown = torch.empty_like(mean)
+            dwork = torch.empty((max(dbytes, 8) // 8,), **f64)
+            _lib.denoise_variance_async(mean.data_ptr(), variance.data_ptr(), dp, shown.data_ptr(),
+                                        dwork.data_ptr() if dbytes else None, dbytes,
+                                        *(aov[k].data_ptr() if aov.get(k) is not None else None
+                                          for k in ("albedo", "normal", "depth")), device=device, stream=stream)
+        rgba = torch.empty((h, w, 4), dtype=torch.uint8, device=where)
+        _lib.linear_to_srgba_async(shown.data_ptr(), h * w, rgba.data_ptr(), device, stream)
+        self.linear[:] = shown.cpu().numpy()
+        self.variance = variance.cpu().numpy()
+        self.counts = counts.cpu().numpy()
+        self.passes = int(self.counts.max())
+        self.imageData[:] = rgba.cpu().numpy()
+        return self.imageData
+
     def RenderLines(self, idx: int, yStart: int, yEnd: int, scene: Scene) -> None:  # ray/tracer.go:120-155
         """Render rows [yStart, yEnd) with the current (initialized) camera and
         fields; like Go, no defaulting happens here."""
