@@ -158,8 +158,9 @@ __host__ __device__ __forceinline__ void sincos_2pi(double u, double& s, double&
 // (tools/sincos_check.hip compares all 2^32 words on the device).
 __host__ __device__ __forceinline__ void sincos_2pi_word(uint32_t w, double& s, double& c) {
     const uint32_t F = w & 0x3FFFFFFFu;
-    const bool swap = F > 0x20000000u;
-    const float x = (float)(swap ? 0x40000000u - F : F) * 0x1p-30f;
+    const bool reflect = F > 0x20000000u;
+    bool swap = reflect;
+    const float x = (float)(reflect ? 0x40000000u - F : F) * 0x1p-30f;
     const float t = x * 0x1.921fb6p+0f;  // RN32(pi/2)
     const float t2 = t * t;
     float sp = __builtin_fmaf(t2, 0x1.71de3ap-19f, -0x1.a01a02p-13f);
@@ -172,6 +173,20 @@ __host__ __device__ __forceinline__ void sincos_2pi_word(uint32_t w, double& s, 
     cp = __builtin_fmaf(cp, t2, 0x1.555556p-5f);
     cp = __builtin_fmaf(cp, t2, -0.5f);
     float cs = __builtin_fmaf(cp, t2, 1.0f);
+    // Quadrant rotation (sincos_2pi's qq == 0: (sk, ck), 1: (ck, -sk), 2: (-sk, -ck),
+    // 3: (-ck, sk)) as a swap on bit 0 and sign flips on the high words: s is
+    // negated in quadrants 2 and 3, c in 1 and 2. Negation is exact, so the bits
+    // are those of the selects it replaces. The swap joins the reflection's, in
+    // FP32 ahead of the Newton step: k is symmetric in the pair (the FP64 squares
+    // are the same two numbers and FP addition commutes), so swapping (sn, cs)
+    // before it gives the bits that swapping (sk, ck) after it did.
+    const uint32_t qq = w >> 30;
+#ifdef TRAY_AB_SINCOS_TWO_SWAPS  // A/B only: the reflection's swap here, the quadrant's in FP64
+    const bool swap_sc = (qq & 1u) != 0u;
+#else
+    const bool swap_sc = false;
+    swap = swap != ((qq & 1u) != 0u);
+#endif
     if (swap) {
         const float tmp = sn;
         sn = cs;
@@ -180,12 +195,6 @@ __host__ __device__ __forceinline__ void sincos_2pi_word(uint32_t w, double& s, 
     const double sd = sn, cd = cs;
     const double k = 1.5 - 0.5 * (sd * sd + cd * cd);
     const double sk = sd * k, ck = cd * k;
-    // Quadrant rotation (sincos_2pi's qq == 0: (sk, ck), 1: (ck, -sk), 2: (-sk, -ck),
-    // 3: (-ck, sk)) as one swap on bit 0 and sign flips on the high words: s is
-    // negated in quadrants 2 and 3, c in 1 and 2. Negation is exact, so the bits
-    // are those of the selects it replaces.
-    const uint32_t qq = w >> 30;
-    const bool swap_sc = (qq & 1u) != 0u;
     const double s0 = swap_sc ? ck : sk, c0 = swap_sc ? sk : ck;
     const uint64_t sflip = (uint64_t)(qq >> 1) << 63, cflip = (uint64_t)((qq ^ (qq >> 1)) & 1u) << 63;
     s = __builtin_bit_cast(double, __builtin_bit_cast(uint64_t, s0) ^ sflip);

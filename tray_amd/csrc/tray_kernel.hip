@@ -977,6 +977,13 @@ __device__ __forceinline__ void write_mean(const KernelParams& p, const double* 
     write_pixel<kFmt>(p, srgb, mean, x, j, pass);
 }
 
+// kAcc, wave-uniform: the mask of every slot of a wave. Read from the kernel arguments where it
+// is used (retiring: rare), not held across the path loop.
+__device__ __forceinline__ uint64_t acc_all_slots(const KernelParams& p) {
+    const uint32_t slots = (uint32_t)p.acc_slots;
+    return slots >= 64u ? ~0ull : (1ull << slots) - 1ull;
+}
+
 // A pixel's fixed-point sums (tray_kernel.hpp): the exact integer total of its
 // r samples, converted to FP64 (one rounding) and scaled back by 2^-acc_shift
 // (exact); a channel with a NaN (non-finite) sample is NaN.
@@ -1461,7 +1468,6 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
     // [acc: waves x acc_slots x groups x kAccSlotBytes][counts: waves x acc_slots x 4 B] at acc_off
     AccCtx acc{nullptr, nullptr};
     uint64_t acc_free = 0;   // kAcc, wave-uniform: free slots
-    uint64_t acc_all = 0;    // kAcc, wave-uniform: every slot
     uint32_t acc_chunk = 0;  // kAcc: lane s holds the chunk of slot s
     if constexpr (kAcc) {
         LdsF64* all = (LdsF64*)reinterpret_cast<double*>(reinterpret_cast<char*>(smem_all) + p.acc_off);
@@ -1472,7 +1478,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
         LdsU32* counts = (LdsU32*)(all + waves * slots * slot_f64);
         for (uint32_t i = threadIdx.x; i < waves * slots; i += blockDim.x) counts[i] = 0u;
         acc.counts = counts + (threadIdx.x / 64u) * slots;
-        acc_free = acc_all = slots >= 64u ? ~0ull : (1ull << slots) - 1ull;
+        acc_free = acc_all_slots(p);
     }
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
@@ -1486,6 +1492,22 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
 
     uint32_t pool_slot = 0;                 // kAcc, wave-uniform: the current chunk's accumulator slot
     uint32_t pool_tile = 0;                 // wave-uniform: the band tile the current chunk renders (work order)
+    // With 64 | r a chunk is 64 samples of one pixel in one pass: its take decodes the pixel once and
+    // the refill's lanes copy it (kChunkPixel; pool_tile and pool_slot are unused). Wave-uniform, of the
+    // current chunk: the column with the accumulator slot above it (pool_xs = x | slot << kXsShift; < 0: a
+    // padding chunk, which starts no sample and takes no slot), the compact row, and the RNG sample
+    // word less the item index: the chunk starts at a multiple of 64 and lies within one pass, so
+    // item i's word is that of the first item + (i & 63). The column fits below the slot: a band holds
+    // tiles_x x 64 x r <= 2^31 items (band_fits) and r >= 64, so x < 8 tiles_x <= 2^22.
+#ifdef TRAY_AB_LANE_DECODE  // A/B only: every instance decodes per lane
+    constexpr bool kChunkPixel = false;
+#else
+    constexpr bool kChunkPixel = kAcc == 1;
+#endif
+    constexpr uint32_t kXsShift = 24u;
+    static_assert(kAccSlotsMax <= 64, "pool_xs: x | slot << 24 stays non-negative");
+    int32_t pool_xs = -1, pool_j = 0;
+    uint32_t pool_sample = 0;
     bool exhausted = false;
 #ifdef TRAY_STATS_GROUND
     uint32_t gcls = 0;  // diagnostic: class of the lane's current segment (1/2: from an out-of-tree sphere, up / other)
@@ -1555,6 +1577,8 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
         // Items are assigned first (cheap, may span two chunks); the camera rays of
         // all newly assigned lanes are then generated together.
         uint32_t fresh_item = ~0u, fresh_slot = 0u, fresh_tile = 0u;
+        int32_t fresh_xs = -1, fresh_j = 0;  // kChunkPixel: the lane's copy of its chunk's pixel and slot
+        uint32_t fresh_sample = 0u;
         bool cam_hit = false;  // a camera ray whose Scene.Hit the candidate list answered in this refill
 #ifdef TRAY_PROFILE_CANDWAIT
         uint64_t prof_wait = 0;
@@ -1571,9 +1595,11 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                     if (acc_free == 0ull) {
                         // Retire the chunks no busy lane traces any more (lanes assigned in
                         // this refill have not started yet: their chunk is open regardless).
-                        const bool held = L.busy || fresh_item != ~0u;
-                        acc_free = acc_retire<kAcc>(kp_fresh(), acc, acc_all, held, L.busy ? L.slot : fresh_slot, acc_chunk,
-                                                    lane);
+                        // (kChunkPixel: a lane given an item of a padding chunk holds no slot.)
+                        const bool held = L.busy || (kChunkPixel ? fresh_xs >= 0 : fresh_item != ~0u);
+                        const uint32_t fresh_held = kChunkPixel ? (uint32_t)fresh_xs >> kXsShift : fresh_slot;
+                        acc_free = acc_retire<kAcc>(kp_fresh(), acc, acc_all_slots(kp_fresh()), held,
+                                                    L.busy ? L.slot : fresh_held, acc_chunk, lane);
                     }
                     if (acc_free == 0ull) {
                         // unreachable with nothing in flight: no chunk would hold a slot
@@ -1605,7 +1631,20 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 pool_end = pool_next + 64u;
                 const KernelParams& pc = kp_fresh();
                 pool_tile = chunk_tile(pc, c);
-                if constexpr (kAcc) {
+                if constexpr (kChunkPixel) {
+                    // Every item of the chunk is one pixel's: valid or padding together, and a
+                    // padding chunk takes no slot.
+                    int32_t cx;
+                    uint32_t cs, cp;
+                    pool_xs = -1;
+                    if (pool_next < pc.items && decode_item(pc, pool_next, pool_tile, cx, pool_j, cs, cp)) {
+                        pool_sample = (pc.pass0 + cp) * (uint32_t)pc.spp + cs - pool_next;
+                        const uint32_t slot = (uint32_t)__builtin_ctzll(acc_free);
+                        acc_free &= ~(1ull << slot);
+                        acc_chunk = lane == slot ? c : acc_chunk;
+                        pool_xs = cx | (int32_t)(slot << kXsShift);
+                    }
+                } else if constexpr (kAcc) {
                     // With 64 | r every item of a chunk is one pixel's: valid or padding
                     // together. A chunk of several pixel-passes (r | 64) may mix the two
                     // and always takes a slot (its padding groups retire as zeros).
@@ -1627,8 +1666,14 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                     __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
                 if (rank < take) {
                     fresh_item = pool_next + rank;
-                    fresh_slot = pool_slot;
-                    fresh_tile = pool_tile;
+                    if constexpr (kChunkPixel) {
+                        fresh_xs = pool_xs;
+                        fresh_j = pool_j;
+                        fresh_sample = pool_sample;
+                    } else {
+                        fresh_slot = pool_slot;
+                        fresh_tile = pool_tile;
+                    }
                 }
             }
             pool_next += take;
@@ -1650,9 +1695,12 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
         if (fresh_item != ~0u) {
             TRAY_MARK("refill_cam")
             const KernelParams& pr = kp_fresh();
-            int32_t x, j;
-            uint32_t smp, pass;
-            if (fresh_item < pr.items && decode_item(pr, fresh_item, fresh_tile, x, j, smp, pass)) {
+            int32_t x = fresh_xs & (int32_t)((1u << kXsShift) - 1u), j = fresh_j;
+            uint32_t smp = 0, pass = 0;
+            bool valid = fresh_xs >= 0;  // kChunkPixel: the chunk's decode
+            if constexpr (!kChunkPixel)
+                valid = fresh_item < pr.items && decode_item(pr, fresh_item, fresh_tile, x, j, smp, pass);
+            if (valid) {
 #ifdef TRAY_PROBE_REFILL
                 TRAY_PROBE_F32(TRAY_PROBE_REFILL)
 #endif
@@ -1660,8 +1708,9 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 uint4 cand = make_uint4(0u, 0u, 0u, kCandOverflow << 16);
                 if constexpr (kBVH)
                     if (pr.cand) cand = pr.cand[(size_t)j * (size_t)pr.width + (size_t)x];
-                start_sample(pr, L, fresh_item, x, j, (pr.pass0 + pass) * (uint32_t)pr.spp + smp);
-                L.slot = fresh_slot;
+                start_sample(pr, L, fresh_item, x, j,
+                             kChunkPixel ? fresh_sample + fresh_item : (pr.pass0 + pass) * (uint32_t)pr.spp + smp);
+                L.slot = kChunkPixel ? (uint32_t)fresh_xs >> kXsShift : fresh_slot;
 #ifdef TRAY_PROFILE_REFILL
                 prof_cam = __builtin_amdgcn_s_memtime();
 #endif
@@ -2005,7 +2054,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
     }
     if constexpr (kProg) flush_progress(kp_fresh(), prog_cur, prog_cnt, lane);
     if constexpr (kAcc)  // every lane is idle
-        (void)acc_retire<kAcc>(kp_fresh(), acc, acc_all & ~acc_free, false, 0u, acc_chunk, lane);
+        (void)acc_retire<kAcc>(kp_fresh(), acc, acc_all_slots(kp_fresh()) & ~acc_free, false, 0u, acc_chunk, lane);
     if constexpr (kStats) {
         // One atomic per wave: 3 per lane on three addresses serialised ~9 ms of tail
         // onto every instrumented launch (786 K device-scope atomics at C2).
