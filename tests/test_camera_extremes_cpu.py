@@ -183,7 +183,7 @@ def fma32(a, b, c):
 
 
 def slab_dir_ok(dirs):
-    """tray_kernel.hip slab_dir_ok: 1e-30 <= |dir|^2 <= 1e30, with Sphere.Hit's own |dir|^2."""
+    """tray_device.hpp slab_dir_ok: 1e-30 <= |dir|^2 <= 1e30, with Sphere.Hit's own |dir|^2."""
     with np.errstate(all="ignore"):
         a = (dirs[:, 0] * dirs[:, 0] + dirs[:, 1] * dirs[:, 1]) + dirs[:, 2] * dirs[:, 2]
         return (a >= 1e-30) & (a <= 1e30)

@@ -14,7 +14,7 @@ import pytest
 
 
 def row_of(j, y_start, tile_rows, tile_count, tile_index):
-    """Compact output row j -> image row (row_of in tray_kernel.hip)."""
+    """Compact output row j -> image row (row_of in tray_device.hpp)."""
     if tile_rows <= 0:
         return y_start + j
     t, within = np.divmod(j, tile_rows)

@@ -21,7 +21,7 @@ def make_fastdiv(d):  # tray_kernel.hpp make_fastdiv
     return d, m & M32, min(l, 1), max(l - 1, 0)
 
 
-def udiv(n, f):  # tray_kernel.hip udiv (32-bit unsigned arithmetic)
+def udiv(n, f):  # tray_device.hpp udiv (32-bit unsigned arithmetic)
     d, m, s1, s2 = f
     t = (n * m) >> 32
     q = ((t + (((n - t) & M32) >> s1)) & M32) >> s2

@@ -1,5 +1,5 @@
 """The begin step of the BVH megakernel (DESIGN.md §5 "The begin step"; lane state
-kTravReady in tray_kernel.hip): the shade phase and the refill's camera-hit shading
+kTravReady in tray_device.hpp): the shade phase and the refill's camera-hit shading
 only mark a scattered ray's lane; one step per loop iteration then sets up the new
 segments of both (|dir|^2, the out-of-tree spheres, the FP32 traversal state). It
 changes when that arithmetic runs, never what it computes, so every frame and every

@@ -1,5 +1,5 @@
 """The scatter step of the BVH megakernel (DESIGN.md §5 "The scatter step"; lane states
-kTravHit / kTravHitCam in tray_kernel.hip): the shade phase and the refill's camera-hit
+kTravHit / kTravHitCam in tray_device.hpp): the shade phase and the refill's camera-hit
 shading run only the end half of a shading (sky, last level) and mark every other hit;
 one step per loop iteration then scatters the marked lanes of both and sets up their new
 segments. It changes when that arithmetic runs, never what it computes, so every frame

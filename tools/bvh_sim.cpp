@@ -7,7 +7,7 @@
 // the ground (out-of-tree spheres) first, then FP32 slab tests of the four
 // child boxes culled by the current hit, the nearest hit child next and the
 // others pushed, one cull per pop (trav_node / trav_leaf / stack_pop in
-// tray_kernel.hip). Counts node visits, box tests and sphere tests per
+// tray_device.hpp). Counts node visits, box tests and sphere tests per
 // segment, and checks every closest hit against the oracle's linear scan.
 //
 //   make -C tools bvh_sim && tools/bvh_sim [pixels] [spp] [leaf_max]

@@ -1,5 +1,5 @@
 // Empirical check of the division-by-known-reciprocal identity used by the
-// kernel (tray_amd/csrc/tray_kernel.hip div_rcp): with y = RN(1/b),
+// kernel (tray_amd/csrc/tray_device.hpp div_rcp): with y = RN(1/b),
 //     q = RN(a*y); r = fma(-b, q, a) (exact); q' = RN(fma(r, y, q))
 // must equal the correctly rounded quotient RN(a/b) (Markstein 1990;
 // Muller et al., Handbook of Floating-Point Arithmetic, 2nd ed., §4.7) away from

@@ -1,7 +1,8 @@
 """tray_amd — MI355X-native renderer for fortio/tray's per-pixel path-tracing loop.
 
 Layout:
-  csrc/          gfx950 megakernel (tray_kernel.hip), C-ABI glue (tray_abi.hip),
+  csrc/          gfx950 megakernel (tray_kernel.hip), the device functions it shares
+                 with the other kernels (tray_device.hpp), C-ABI glue (tray_abi.hip),
                  host setup (tray_host.cpp); built into libtray_amd.so
   _lib.py        ctypes binding of include/tray.h (no fallback path)
   ray.py         mirror of the Go `ray` package API (New/Render/RenderLines/...)

@@ -623,6 +623,39 @@ static void key_params(uint64_t seed, KernelParams& k) {
     k.key[0] = dk.k0, k.key[1] = dk.k1, k.key[2] = dk.k2, k.key[3] = dk.k3;
 }
 
+// The image, row-set, pass, camera and draw-key fields of the kernel parameters: `n_passes`
+// passes, from p->pass on, of the `rows` = tray_params_rows(p) rows of p's row set.
+static void frame_params(const tray_camera* cam, const tray_params* p, int32_t rows, int32_t n_passes,
+                         KernelParams& k) {
+    k.width = p->width;
+    k.height = p->height;
+    k.spp = p->rays_per_pixel;
+    k.max_depth = p->max_depth;
+    k.y_start = p->y_start;
+    k.rows = rows;
+    k.tile_rows = p->tile_rows;
+    k.tile_count = p->tile_rows > 0 ? p->tile_count : 1;
+    k.tile_index = p->tile_rows > 0 ? p->tile_index : 0;
+    k.ray_radius = p->ray_radius;
+    k.passes = (uint32_t)n_passes;
+    k.pass0 = (uint32_t)p->pass;
+    camera_params(cam, k);
+    key_params(p->seed, k);
+}
+
+// n_passes passes from p->pass on (p validated): at least one, and their sample words fit 32 bits.
+static int validate_passes(const tray_params* p, int32_t n_passes) {
+    if (n_passes < 1) return fail(TRAY_ERR_INVALID_ARGUMENT, "n_passes must be >= 1");
+    if (((uint64_t)p->pass + (uint64_t)n_passes) * (uint64_t)p->rays_per_pixel > 0x100000000ull)
+        return fail(TRAY_ERR_TOO_LARGE, "(pass + n_passes) x rays_per_pixel exceeds the 32-bit RNG sample word");
+    return TRAY_OK;
+}
+
+// The caller's choice between the scene's BVH and the reference-order linear scan.
+static bool wants_bvh(const tray_scene_s* sc, int32_t flags) {
+    return sc->has_bvh && !(flags & TRAY_FLAG_LINEAR_SCAN);
+}
+
 // The kernel parameters of a render of `p` on `sc` (everything but the output,
 // instrumentation and workspace pointers) and whether it runs the BVH kernel.
 static int prepare_render(tray_scene_t sc, const tray_camera* cam, const tray_params* p, int32_t n_passes,
@@ -630,27 +663,15 @@ static int prepare_render(tray_scene_t sc, const tray_camera* cam, const tray_pa
     if (!sc || !cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null argument");
     int rc = validate_params(p);
     if (rc) return rc;
-    if (n_passes < 1) return fail(TRAY_ERR_INVALID_ARGUMENT, "n_passes must be >= 1");
-    if (((uint64_t)p->pass + (uint64_t)n_passes) * (uint64_t)p->rays_per_pixel > 0x100000000ull)
-        return fail(TRAY_ERR_TOO_LARGE, "(pass + n_passes) x rays_per_pixel exceeds the 32-bit RNG sample word");
+    rc = validate_passes(p, n_passes);
+    if (rc) return rc;
     const uint64_t spp_launch = (uint64_t)p->rays_per_pixel * (uint64_t)n_passes;
     if (!band_fits(p->width, spp_launch))
         return fail(TRAY_ERR_TOO_LARGE, "width x rays_per_pixel x passes too large (8 rows of samples exceed 2^31)");
     memset(&k, 0, sizeof(k));
     scene_params(sc, k);
-    k.width = p->width;
-    k.height = p->height;
-    k.spp = p->rays_per_pixel;
-    k.max_depth = p->max_depth;
-    k.y_start = p->y_start;
-    k.rows = tray_params_rows(p);
-    k.tile_rows = p->tile_rows;
-    k.tile_count = p->tile_rows > 0 ? p->tile_count : 1;
-    k.tile_index = p->tile_rows > 0 ? p->tile_index : 0;
+    frame_params(cam, p, tray_params_rows(p), n_passes, k);
     k.out_format = p->output;
-    k.ray_radius = p->ray_radius;
-    camera_params(cam, k);
-    key_params(p->seed, k);
     k.acc_shift = fixed_point_shift(sc, p);
     if (k.acc_shift > 0) {  // the scale rides on the background: every colour is then scaled (exactly)
         for (V3* v : {&k.bg_a, &k.bg_b}) {
@@ -659,8 +680,6 @@ static int prepare_render(tray_scene_t sc, const tray_camera* cam, const tray_pa
             v->z = std::ldexp(v->z, k.acc_shift);
         }
     }
-    k.passes = (uint32_t)n_passes;
-    k.pass0 = (uint32_t)p->pass;
     k.out_frame_bytes = (size_t)k.rows * (size_t)p->width * bytes_per_pixel(p->output);
     {
         long long coop = TRAY_COOP_LANES;
@@ -676,7 +695,7 @@ static int prepare_render(tray_scene_t sc, const tray_camera* cam, const tray_pa
     // A scene with an infinite or NaN albedo renders through the linear scan: the
     // one kernel instance that multiplies an ended path's black by its attenuations
     // as Go's recursion does (tray_kernel.hip shade_step, kWild).
-    use_bvh = sc->has_bvh && !(p->flags & TRAY_FLAG_LINEAR_SCAN) && cam_extent <= sc->bvh_bound && k.wild_att == 0;
+    use_bvh = wants_bvh(sc, p->flags) && cam_extent <= sc->bvh_bound && k.wild_att == 0;
     return TRAY_OK;
 }
 
@@ -891,7 +910,6 @@ int tray_render_stats_async(tray_scene_t sc, const tray_camera* cam, const tray_
                              stream);
 }
 
-// Grows a device workspace to `bytes` (contents not kept).
 // ---- ray queries (include/tray_query.h) ----------------------------------------
 int32_t tray_query_version(void) { return TRAY_QUERY_VERSION; }
 
@@ -924,19 +942,7 @@ int tray_camera_rays_async(const tray_camera* cam, const tray_params* p, int32_t
     if (rc) return rc;
     KernelParams k;
     memset(&k, 0, sizeof(k));
-    k.width = p->width;
-    k.height = p->height;
-    k.spp = p->rays_per_pixel;
-    k.y_start = p->y_start;
-    k.rows = (int32_t)rows;
-    k.tile_rows = p->tile_rows;
-    k.tile_count = p->tile_rows > 0 ? p->tile_count : 1;
-    k.tile_index = p->tile_rows > 0 ? p->tile_index : 0;
-    k.ray_radius = p->ray_radius;
-    k.passes = 1;
-    k.pass0 = (uint32_t)p->pass;
-    camera_params(cam, k);
-    key_params(p->seed, k);
+    frame_params(cam, p, (int32_t)rows, 1, k);
     TRAY_HIP(hipSetDevice(device));
     TRAY_HIP(launch_camera_rays(k, rays_device, ids_device, (uint32_t)n, static_cast<hipStream_t>(stream)));
     return TRAY_OK;
@@ -952,8 +958,8 @@ int tray_scene_hit_async(tray_scene_t sc, const tray_ray* rays_device, int64_t n
     memset(&k, 0, sizeof(k));
     scene_params(sc, k);
     TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_scene_hit(k, sc->has_bvh && !(flags & TRAY_FLAG_LINEAR_SCAN), sc->bvh_bound, rays_device,
-                              (uint32_t)n, t_end, hits_device, static_cast<hipStream_t>(stream)));
+    TRAY_HIP(launch_scene_hit(k, wants_bvh(sc, flags), sc->bvh_bound, rays_device, (uint32_t)n, t_end, hits_device,
+                              static_cast<hipStream_t>(stream)));
     return TRAY_OK;
 }
 
@@ -970,9 +976,8 @@ int tray_ray_color_async(tray_scene_t sc, const tray_ray* rays_device, const uin
     key_params(seed, k);
     k.max_depth = max_depth;
     TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_ray_color(k, sc->has_bvh && !(flags & TRAY_FLAG_LINEAR_SCAN), sc->bvh_bound, rays_device,
-                              ids_device, (uint32_t)n, rgb_device, segments_device,
-                              static_cast<hipStream_t>(stream)));
+    TRAY_HIP(launch_ray_color(k, wants_bvh(sc, flags), sc->bvh_bound, rays_device, ids_device, (uint32_t)n, rgb_device,
+                              segments_device, static_cast<hipStream_t>(stream)));
     return TRAY_OK;
 }
 
@@ -1023,9 +1028,8 @@ int tray_scene_occluded_async(tray_scene_t sc, const tray_ray* rays_device, cons
     memset(&k, 0, sizeof(k));
     scene_params(sc, k);
     TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_scene_occluded(k, sc->has_bvh && !(flags & TRAY_FLAG_LINEAR_SCAN), sc->bvh_bound, rays_device,
-                                   t_end_device, (uint32_t)n, t_end, occluded_device,
-                                   static_cast<hipStream_t>(stream)));
+    TRAY_HIP(launch_scene_occluded(k, wants_bvh(sc, flags), sc->bvh_bound, rays_device, t_end_device, (uint32_t)n,
+                                   t_end, occluded_device, static_cast<hipStream_t>(stream)));
     return TRAY_OK;
 }
 
@@ -1050,22 +1054,9 @@ int tray_render_aov_async(tray_scene_t sc, const tray_camera* cam, const tray_pa
     KernelParams k;
     memset(&k, 0, sizeof(k));
     scene_params(sc, k);
-    k.width = p->width;
-    k.height = p->height;
-    k.spp = p->rays_per_pixel;
-    k.y_start = p->y_start;
-    k.rows = (int32_t)rows;
-    k.tile_rows = p->tile_rows;
-    k.tile_count = p->tile_rows > 0 ? p->tile_count : 1;
-    k.tile_index = p->tile_rows > 0 ? p->tile_index : 0;
-    k.ray_radius = p->ray_radius;
-    k.passes = 1;
-    k.pass0 = (uint32_t)p->pass;
-    camera_params(cam, k);
-    key_params(p->seed, k);
+    frame_params(cam, p, (int32_t)rows, 1, k);
     TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_render_aov(k, sc->has_bvh && !(p->flags & TRAY_FLAG_LINEAR_SCAN), sc->bvh_bound, *out,
-                               static_cast<hipStream_t>(stream)));
+    TRAY_HIP(launch_render_aov(k, wants_bvh(sc, p->flags), sc->bvh_bound, *out, static_cast<hipStream_t>(stream)));
     return TRAY_OK;
 }
 
@@ -1080,9 +1071,8 @@ int tray_render_pixels_async(tray_scene_t sc, const tray_camera* cam, const tray
     if (p->output != TRAY_OUT_RGB_F64)
         return fail(TRAY_ERR_INVALID_ARGUMENT, "a pixel list renders TRAY_OUT_RGB_F64 only");
     if (n_pixels < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative n_pixels");
-    if (n_passes < 1) return fail(TRAY_ERR_INVALID_ARGUMENT, "n_passes must be >= 1");
-    if (((uint64_t)p->pass + (uint64_t)n_passes) * (uint64_t)p->rays_per_pixel > 0x100000000ull)
-        return fail(TRAY_ERR_TOO_LARGE, "(pass + n_passes) x rays_per_pixel exceeds the 32-bit RNG sample word");
+    rc = validate_passes(p, n_passes);
+    if (rc) return rc;
     const int64_t rows = tray_params_rows(p);
     if (rows * (int64_t)p->width > kQueryMaxRays)
         return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one row set");
@@ -1096,35 +1086,12 @@ int tray_render_pixels_async(tray_scene_t sc, const tray_camera* cam, const tray
     KernelParams k;
     memset(&k, 0, sizeof(k));
     scene_params(sc, k);
-    k.width = p->width;
-    k.height = p->height;
-    k.spp = p->rays_per_pixel;
-    k.max_depth = p->max_depth;
-    k.y_start = p->y_start;
-    k.rows = (int32_t)rows;
-    k.tile_rows = p->tile_rows;
-    k.tile_count = p->tile_rows > 0 ? p->tile_count : 1;
-    k.tile_index = p->tile_rows > 0 ? p->tile_index : 0;
-    k.ray_radius = p->ray_radius;
-    k.passes = (uint32_t)n_passes;
-    k.pass0 = (uint32_t)p->pass;
-    camera_params(cam, k);
-    key_params(p->seed, k);
+    frame_params(cam, p, (int32_t)rows, n_passes, k);
     TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_render_pixels(k, sc->has_bvh && !(p->flags & TRAY_FLAG_LINEAR_SCAN), sc->bvh_bound, pixels_device,
-                                  (uint32_t)n_pixels, pass_plane_device, (uint32_t)n_passes, out_device,
-                                  segments_device, static_cast<hipStream_t>(stream)));
+    TRAY_HIP(launch_render_pixels(k, wants_bvh(sc, p->flags), sc->bvh_bound, pixels_device, (uint32_t)n_pixels,
+                                  pass_plane_device, (uint32_t)n_passes, out_device, segments_device,
+                                  static_cast<hipStream_t>(stream)));
     return TRAY_OK;
-}
-
-static hipError_t grow(void** buf, size_t* have, size_t bytes) {
-    if (*have >= bytes) return hipSuccess;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    const hipError_t e = hipMalloc(buf, bytes);
-    if (e == hipSuccess) *have = bytes;
-    return e;
 }
 
 // The scene of a slot: its cached upload when the caller passes the same
@@ -1168,6 +1135,17 @@ static int cached_scene(Slot& sl, const tray_sphere* spheres, int32_t n, const t
     }
     *out = sl.cached;
     return TRAY_OK;
+}
+
+// Grows a device workspace of a slot to `bytes` (contents not kept).
+static hipError_t grow(void** buf, size_t* have, size_t bytes) {
+    if (*have >= bytes) return hipSuccess;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    *have = 0;
+    const hipError_t e = hipMalloc(buf, bytes);
+    if (e == hipSuccess) *have = bytes;
+    return e;
 }
 
 // Stream and output workspaces of a slot for `npix` pixels.

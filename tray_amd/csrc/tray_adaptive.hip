@@ -2,22 +2,22 @@
 // list (section 2), Welford's fold with a count per pixel (section 3) and the
 // selection step (section 4: metric, dilation, ascending compaction).
 //
-// The renderer's arithmetic is the megakernel's and the queries': this file includes
-// tray_query.hip's device functions (query_hit, query_shade with its scatter_step,
-// the stack policy) and through it tray_kernel.hip's (get_ray, camera_block, row_of,
-// kp_fresh, ...), and leaves their kernels and host sides out. Compiled with
-// -ffp-contract=off like every other unit; the header is the contract.
+// The renderer's arithmetic is the megakernel's and the queries': it comes from
+// tray_query_device.hpp (query_hit, query_shade with its scatter_step, the stack
+// policy, query_args) and, under that, tray_device.hpp (get_ray, camera_block, row_of,
+// kp_fresh, ...). The metric pass streams the state the way accum_fold_kernel does,
+// through tray_stream.hpp. Compiled with -ffp-contract=off like every other unit; the
+// public header is the contract.
 
-#define TRAY_DEVICE_FUNCTIONS_ONLY
-#define TRAY_QUERY_DEVICE_FUNCTIONS_ONLY
-#include "tray_query.hip"
-
+#include <algorithm>
 #include <cmath>
 #include <limits>
 #include <string>
 
 #include "../../include/tray_adaptive.h"
 #include "tray_internal.hpp"
+#include "tray_query_device.hpp"
+#include "tray_stream.hpp"
 
 namespace tray {
 
@@ -266,9 +266,9 @@ __global__ __launch_bounds__(kFoldThreads) void adaptive_fold_kernel(const Spars
 
 // ---- section 4: the selection --------------------------------------------------------
 //
-// Four launches. (1) The metric pass streams the state as accum_fold_kernel does (a wave
-// owns 384 consecutive doubles = 128 pixels, read and written as 16-byte pairs declared
-// 8-byte aligned, then transposed through LDS to pixels), with the one difference that D
+// Four launches. (1) The metric pass streams the state as accum_fold_kernel does
+// (tray_stream.hpp: a wave owns 384 consecutive doubles = 128 pixels, read and written as
+// 16-byte pairs, then transposed through LDS to pixels), with the one difference that D
 // is per pixel: each element divides by the D of pixel e / 3, from a gathered count. It
 // writes the variance, the needs flag of every pixel (one byte, the workspace's flag
 // plane) and the record's three sums. (2) A workgroup per 1024 pixels counts its active
@@ -276,16 +276,7 @@ __global__ __launch_bounds__(kFoldThreads) void adaptive_fold_kernel(const Spars
 // max_passes) into the block totals. (3) One wave scans the totals in place and writes
 // n_active. (4) The workgroups of (2) evaluate their pixels again and write the active
 // indices at their block's offset: ballots in ascending pixel order, so the list ascends.
-constexpr int kWave = 64;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kSlots = 3;                        // 16-byte accesses per lane and image
-constexpr int kRowElems = 2 * kWave;             // doubles one wave access covers
-constexpr int kWaveElems = kSlots * kRowElems;   // 384 doubles = 128 pixels
-constexpr int kWavePixels = kWaveElems / 3;
-constexpr int kBlockElems = kWaves * kWaveElems; // 1536 doubles = 512 pixels
-constexpr int64_t kMaxGrid = 2048;               // 8 workgroups for each of 256 CUs
-constexpr uint32_t kScanPixels = 1024;           // pixels per block total (the header's formula)
+constexpr uint32_t kScanPixels = 1024;  // pixels per block total (the header's formula)
 
 struct SelectArgs {
     const double* mean;
@@ -302,31 +293,6 @@ struct SelectArgs {
     int32_t min_passes, max_passes, dilate;
     double T, floor;
 };
-
-struct __attribute__((packed, aligned(8))) Pair {  // 16 bytes at 8-byte alignment
-    double a, b;
-};
-
-__device__ __forceinline__ void load_pair(const double* base, size_t i, size_t elems, double& a, double& b) {
-    if (i + 1 < elems) {
-        const Pair v = *reinterpret_cast<const Pair*>(base + i);
-        a = v.a;
-        b = v.b;
-    } else if (i < elems) {
-        a = base[i];
-    }
-}
-
-__device__ __forceinline__ void store_pair(double* base, size_t i, size_t elems, double a, double b) {
-    if (i + 1 < elems) {
-        Pair v;
-        v.a = a;
-        v.b = b;
-        *reinterpret_cast<Pair*>(base + i) = v;
-    } else if (i < elems) {
-        base[i] = a;
-    }
-}
 
 // variance of element e (of pixel e / 3) from its m2: +inf below two passes.
 __device__ __forceinline__ double variance_of(const SelectArgs& A, size_t e, double m2) {

@@ -34,20 +34,12 @@
 
 #include "../../include/tray_progressive.h"
 #include "tray_internal.hpp"
+#include "tray_stream.hpp"
 
 namespace tray {
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kSlots = 3;                            // 16-byte accesses per lane and image
-constexpr int kRowElems = 2 * kWave;                 // doubles one wave access covers
-constexpr int kWaveElems = kSlots * kRowElems;       // 384 doubles = 128 pixels
-constexpr int kWavePixels = kWaveElems / 3;
-constexpr int kBlockElems = kWaves * kWaveElems;     // 1536 doubles = 512 pixels
-constexpr int kFramesAhead = 4;
-constexpr int64_t kMaxGrid = 2048;                   // 8 workgroups for each of 256 CUs
+constexpr int kFramesAhead = 4;  // frames fetched ahead of the divide chains
 
 struct FoldArgs {
     double* mean;
@@ -64,31 +56,6 @@ struct FoldArgs {
     double T;              // tolerance * tolerance
     double floor;
 };
-
-struct __attribute__((packed, aligned(8))) Pair {  // 16 bytes at 8-byte alignment
-    double a, b;
-};
-
-__device__ __forceinline__ void load_pair(const double* base, size_t i, size_t elems, double& a, double& b) {
-    if (i + 1 < elems) {
-        const Pair v = *reinterpret_cast<const Pair*>(base + i);
-        a = v.a;
-        b = v.b;
-    } else if (i < elems) {
-        a = base[i];
-    }
-}
-
-__device__ __forceinline__ void store_pair(double* base, size_t i, size_t elems, double a, double b) {
-    if (i + 1 < elems) {
-        Pair v;
-        v.a = a;
-        v.b = b;
-        *reinterpret_cast<Pair*>(base + i) = v;
-    } else if (i < elems) {
-        base[i] = a;
-    }
-}
 
 template <bool kMetric>
 __global__ __launch_bounds__(kThreads) void accum_fold_kernel(const FoldArgs A) {

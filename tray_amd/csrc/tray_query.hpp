@@ -1,5 +1,8 @@
 // Internal launch interface between the C-ABI glue (tray_abi.hip) and the
-// ray-query kernels (tray_query.hip, include/tray_query.h and tray_shade.h).
+// ray-query kernels (tray_query.hip: include/tray_query.h, tray_shade.h and
+// tray_aov.h) and the pixel-list renderer (tray_adaptive.hip). Host side only:
+// the device functions those two units share are tray_query_device.hpp, over
+// tray_device.hpp, which the megakernel (tray_kernel.hip) compiles too.
 // Not part of the public ABI.
 #pragma once
 
