@@ -2,7 +2,7 @@
 """Diagnostic: where a launch's ramp and drain go. Needs a -DTRAY_PROFILE_TIMELINE
 build (tools/build_variants.sh tl "-DTRAY_PROFILE_TIMELINE"); renders one frame
 through the stats instance and reports, from every wave's record
-(tray_kernel.hip, kTlStride): busy lanes of the whole grid over time (10-us
+(tray_diag.hpp, kTlStride): busy lanes of the whole grid over time (10-us
 buckets), the time the work queue first and last ran dry in a wave, wave end
 times, chunks per wave, and the lane-time lost before the first dry wave, between
 first dry and the last wave's end.

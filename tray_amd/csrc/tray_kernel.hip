@@ -38,7 +38,7 @@
 
 #include <algorithm>
 
-#include "tray_device.hpp"
+#include "tray_diag.hpp"  // the diagnostic builds' hooks; it includes tray_device.hpp
 
 namespace tray {
 
@@ -631,141 +631,6 @@ constexpr int32_t kDeepNodes = 384;
 // behind it (C2 -0.30 %, C5 -0.39 %; levels 1-3 alike; raising it instead for the
 // node steps, the camera rays or the shading phase gained nothing or lost).
 
-// Cost probes (diagnostic builds only, never timed as the product): N extra
-// independent VALU instructions in one phase, to measure what an instruction
-// there costs (tools/ab_bench.py A/B against the plain build).
-#define TRAY_PROBE_F32(n)                                                     \
-    {                                                                         \
-        _Pragma("unroll") for (int i_ = 0; i_ < (n); ++i_) {                  \
-            float t_;                                                         \
-            asm volatile("v_add_f32_e64 %0, 1.0, 1.0" : "=v"(t_));            \
-        }                                                                     \
-    }
-#define TRAY_PROBE_F64(n)                                                     \
-    {                                                                         \
-        _Pragma("unroll") for (int i_ = 0; i_ < (n); ++i_) {                  \
-            double t_;                                                        \
-            asm volatile("v_add_f64 %0, 1.0, 1.0" : "=v"(t_));                \
-        }                                                                     \
-    }
-
-// ISA census build only (-DTRAY_CENSUS, tools/isa_census.py): a comment in the
-// assembly where each phase of the BVH loop starts, so the census can attribute
-// instructions to phases. Never in a timed build.
-#ifdef TRAY_CENSUS
-#define TRAY_MARK(name) asm volatile(";@phase " name);
-#else
-#define TRAY_MARK(name)
-#endif
-
-// Diagnostic build only (-DTRAY_PROFILE): per-wave s_memtime stamps around each
-// phase of the BVH loop, plus phase and active-lane counts, added into
-// stats[3..29] (the stats buffer must then hold 30 counters). Never part of a
-// timed build: the stamps' waits serialise the phases.
-// Slots 0-15 go to stats[3..18], slots 16-23 to stats[22..29]: [16] cycles, [17] passes,
-// [18] lanes of the refill's end half (its cycles are inside slot 0's too); [19] cycles,
-// [20] passes, [21] lanes of the scatter step's scatter part; [22] lanes absorbed in it;
-// [23] cycles of its begin part.
-// With -DTRAY_PROFILE_BEGIN the census of the scatter step's sources replaces slots 10-12
-// (tools/phase_profile.py --begin): [10] / [11] hits marked by the shade phase /
-// by the refill's camera-hit shading, as (passes << 40) + lanes; [12] (refills that
-// found lanes marked by the shade phase just before << 40) + lanes of the scatter
-// steps. Slot 15 counts the scatter steps that begin a segment in every profile build.
-#ifdef TRAY_PROFILE
-// Counters live in LDS (per wave, lane 0 adds): registers would change the
-// kernel being measured.
-#define PROF_T0() const uint64_t prof_t0_ = __builtin_amdgcn_s_memtime()
-#define PROF_ADD(slot) PROF_CNT(slot, __builtin_amdgcn_s_memtime() - prof_t0_)
-#define PROF_CNT(slot, v)                                  \
-    {                                                      \
-        const unsigned long long v_ = (v);                 \
-        if (lane == 0) atomicAdd(prof + (slot), v_);       \
-    }
-// A stamp pair nested in another phase's, or on a slot the timeline build has none for.
-#define PROF_T0E() PROF_T0()
-#define PROF_ADDE(slot) PROF_ADD(slot)
-#elif defined(TRAY_PROFILE_TIMELINE)
-// The timeline build times the phases of a wave's lone last path (refill, node steps,
-// leaves, shading: tl_ph[0..3]).
-#define PROF_T0() const uint64_t prof_t0_ = (kStats && tl_lone) ? __builtin_amdgcn_s_memtime() : 0
-#define PROF_ADD(slot) \
-    if (kStats && tl_lone) tl_ph[slot] += __builtin_amdgcn_s_memtime() - prof_t0_
-#define PROF_CNT(slot, v)
-#else
-#define PROF_T0()
-#define PROF_ADD(slot)
-#define PROF_CNT(slot, v)
-#endif
-#ifndef TRAY_PROFILE
-#define PROF_T0E()
-#define PROF_ADDE(slot)
-#endif
-
-// Diagnostic build only (-DTRAY_PROFILE -DTRAY_PROFILE_MATERIAL): the divergence
-// census of the scatter step's passes. Per site (the marked lanes that come 0: from
-// the refill's camera-hit shading, 1: from the shade phase) and per class of lane (0
-// miss/sky and 1 hit at the last level: none since the end half serves them, 2
-// Lambertian, 3 Metal without fuzz, 4 Metal with fuzz, 5 Dielectric): [c] passes with such a lane, [6 + c] such lanes; [12 + b] passes
-// executing b of the three material bodies (b = 0..3); [16] passes, [17] lanes;
-// [18 + h] / [22 + h] passes with 1, 2-3, 4-7, >= 8 Dielectric / Metal lanes.
-// Added with global atomics after the per-wave stamps (stats[32 + 2 x waves + k]).
-#if defined(TRAY_PROFILE_BEGIN) && (defined(TRAY_PROFILE_REFILL) || defined(TRAY_PROFILE_CANDWAIT))
-#error "TRAY_PROFILE_BEGIN shares profile slots with TRAY_PROFILE_REFILL / TRAY_PROFILE_CANDWAIT"
-#endif
-#ifdef TRAY_PROFILE_MATERIAL
-constexpr int kMatCounters = 26;
-__device__ __forceinline__ void prof_material(int site, bool active, int32_t slot, uint32_t bounce, int32_t max_depth,
-                                              const MatRec* bmat, uint32_t lane, unsigned long long* pm) {
-    int cls = -1;
-    if (active) {
-        if (slot < 0) cls = 0;
-        else if (bounce + 1u >= (uint32_t)max_depth) cls = 1;
-        else {
-            const MatRec& m = bmat[slot];
-            cls = m.type == kLambertian ? 2 : m.type == kDielectric ? 5 : m.param > 0.0 ? 4 : 3;
-        }
-    }
-    unsigned long long* c = pm + site * kMatCounters;
-    int bodies = 0;
-    for (int k = 0; k < 6; ++k) {
-        const uint64_t m = __ballot(cls == k);
-        if (lane == 0 && m) {
-            atomicAdd(c + k, 1ull);
-            atomicAdd(c + 6 + k, (unsigned long long)__popcll(m));
-        }
-    }
-    bodies = (__ballot(cls == 2) ? 1 : 0) + (__ballot(cls == 3 || cls == 4) ? 1 : 0) + (__ballot(cls == 5) ? 1 : 0);
-    const int n_di = __popcll(__ballot(cls == 5)), n_me = __popcll(__ballot(cls == 3 || cls == 4));
-    const int n_active = __popcll(__ballot(active));  // ahead of the branch: inside it only lane 0 votes
-    if (lane == 0) {
-        if (n_di) atomicAdd(c + 18 + (n_di >= 8 ? 3 : n_di >= 4 ? 2 : n_di >= 2 ? 1 : 0), 1ull);
-        if (n_me) atomicAdd(c + 22 + (n_me >= 8 ? 3 : n_me >= 4 ? 2 : n_me >= 2 ? 1 : 0), 1ull);
-        atomicAdd(c + 12 + bodies, 1ull);
-        atomicAdd(c + 16, 1ull);
-        atomicAdd(c + 17, (unsigned long long)n_active);
-    }
-}
-#define PROF_MATERIAL(site, active) prof_material(site, active, T.slot, L.bounce, p.max_depth, p.bmat, lane, prof_mat)
-#else
-#define PROF_MATERIAL(site, active)
-#endif
-
-// Diagnostic build only (-DTRAY_PROFILE_TIMELINE, stats instance; tools/timeline.py):
-// per wave, busy lanes integrated over time in kTlTicks buckets of the shader clock
-// (s_memtime, read once per loop iteration; the 100 MHz constant clock, s_memrealtime,
-// only at the wave's start, dry point and end: read per iteration it stalled waves),
-// constant clock, relative to the wave's start, plus its start, end, the time its
-// queue ran dry and the chunks it took. Record of wave w at stats[32 + w x kTlStride]:
-// [0] start, [1] end, [2] exhausted (ticks after start), [3] chunks, [4..] buckets.
-#ifdef TRAY_PROFILE_TIMELINE
-// [0] start, [1] end, [2] dry (constant clock), [3] chunks, [4] / [5] shader clock at start / end,
-// [6 ..] buckets; the last nine: the shader ticks the wave's lone last path spent in the
-// refill, node-step, leaf and shading phases, when it became the wave's only path
-// (shader ticks after the start) and its segments then, and that path's segments,
-// pixel and sample at the end (its latency per segment with no other path in the wave).
-constexpr uint32_t kTlBuckets = 1024, kTlTicks = 25000, kTlHdr = 6, kTlStride = kTlBuckets + kTlHdr;
-#endif
-
 // Sum of a per-lane 64-bit counter over the wave (instrumented instances only).
 __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 #pragma unroll
@@ -901,68 +766,17 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
     int32_t pool_xs = -1, pool_j = 0;
     uint32_t pool_sample = 0;
     bool exhausted = false;
-#ifdef TRAY_STATS_GROUND
-    uint32_t gcls = 0;  // diagnostic: class of the lane's current segment (1/2: from an out-of-tree sphere, up / other)
-#endif
     int32_t prog_cur = 0;  // live progress: the wave's current tile row and its unflushed count
     uint64_t prog_cnt = 0;
-#ifdef TRAY_PROFILE
-    __shared__ unsigned long long prof_lds[16 * 24];
-    unsigned long long* prof = prof_lds + 24 * (threadIdx.x / 64u);
-    if (lane == 0)
-        for (int i = 0; i < 24; ++i) prof[i] = 0;
-    const uint64_t prof_start = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef TRAY_PROFILE_MATERIAL  // counts only (global atomics: its timings are not used)
-    unsigned long long* prof_mat = p.stats + 32 + 2 * gridDim.x * (blockDim.x / 64u);
-#endif
-#ifdef TRAY_PROFILE_TIMELINE
-    unsigned long long* tl =  // only the stats instance has a buffer; every use is under kStats
-        kStats ? p.stats + 32 + (size_t)(blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u) * kTlStride : nullptr;
-    const uint64_t tl_start = __builtin_amdgcn_s_memrealtime(), tl_mt0 = __builtin_amdgcn_s_memtime();
-    uint64_t tl_prev = tl_mt0, tl_acc = 0;
-    uint32_t tl_busy = 0, tl_bucket = 0, tl_chunks = 0, tl_dry = 0;
-    bool tl_lone = false;
-    uint64_t tl_ph[4] = {0, 0, 0, 0};
-#endif
+    // The diagnostic builds' state and hooks (tray_diag.hpp). Every call stands under the hook's constant
+    // (true where it has a body): even an empty call here changes the device code.
+    Diag dg;
+    if constexpr (Diag::kKernelBegin<kStats>) dg.kernel_begin<kStats>(p, lane);
 
     while (true) {
-#ifdef TRAY_PROFILE_TIMELINE
-        if constexpr (kStats) {  // p.stats is null in every other instance
-            const uint64_t now = __builtin_amdgcn_s_memtime();
-            const uint32_t b = min((uint32_t)((tl_prev - tl_mt0) / kTlTicks), kTlBuckets - 10u);
-            if (b != tl_bucket) {
-                if (lane == 0) tl[kTlHdr + tl_bucket] = tl_acc;
-                tl_bucket = b;
-                tl_acc = 0;
-            }
-            tl_acc += (now - tl_prev) * tl_busy;
-            tl_prev = now;
-            // The wave's last path after its queue ran dry: its segments so far, pixel, sample.
-            const uint64_t m = __ballot(L.busy);
-            if (exhausted && __popcll(m) == 1) {
-                const uint32_t l = (uint32_t)__builtin_ctzll(m);
-                const uint32_t seg = __builtin_amdgcn_readlane(L.segments, l);
-                const uint32_t pix = __builtin_amdgcn_readlane(L.pixel, l);
-                const uint32_t smp = __builtin_amdgcn_readlane(L.sample, l);
-                if (lane == 0) {
-                    if (!tl_lone) {
-                        tl[kTlHdr + kTlBuckets - 5] = now - tl_mt0;
-                        tl[kTlHdr + kTlBuckets - 4] = seg;
-                    }
-                    tl[kTlHdr + kTlBuckets - 3] = seg;
-                    tl[kTlHdr + kTlBuckets - 2] = pix;
-                    tl[kTlHdr + kTlBuckets - 1] = smp;
-                }
-                tl_lone = true;
-            }
-        }
-#endif
-#if !defined(TRAY_PROFILE_REFILL) && !defined(TRAY_PROFILE_BEGIN)  // slots 10, 13-15 hold the refill split
-        PROF_CNT(10, 1);                                               // instead, or 10-12 the begin-step census
-#endif
+        if constexpr (Diag::kIteration<kStats>) dg.iteration<kStats>(lane, exhausted, L.busy, L.segments, L.pixel, L.sample);
         // Refill idle lanes from the wave's pool, fetching 64-item chunks from the global queue.
-        PROF_T0();
+        if constexpr (Diag::kPhase<kStats>) dg.phase_begin<kStats>();
         TRAY_MARK("refill_assign")
         uint64_t idle = __ballot(!L.busy);
         if (__popcll(idle) < TRAY_REFILL_BATCH && idle != ~0ull) idle = 0ull;  // batch refills
@@ -972,12 +786,6 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
         int32_t fresh_xs = -1, fresh_j = 0;  // kChunkPixel: the lane's copy of its chunk's pixel and slot
         uint32_t fresh_sample = 0u;
         bool cam_hit = false;  // a camera ray whose Scene.Hit the candidate list answered in this refill
-#ifdef TRAY_PROFILE_CANDWAIT
-        uint64_t prof_wait = 0;
-#endif
-#ifdef TRAY_PROFILE_REFILL
-        uint64_t prof_cam = 0, prof_hit = 0;  // stamps after the camera ray / after its Scene.Hit
-#endif
         while (idle != 0ull && !exhausted) {
             if (pool_next == pool_end) {
                 if constexpr (kAcc) {
@@ -1008,14 +816,10 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                     c = take_chunk(pq, uni, lane, grp_end >= pq.late_at ? 1u : pq.wave_chunks, cnt);
                     if (c == kPoolDone) {
                         exhausted = true;
-#ifdef TRAY_PROFILE_TIMELINE
-                        if constexpr (kStats) tl_dry = (uint32_t)(__builtin_amdgcn_s_memrealtime() - tl_start);
-#endif
+                        if constexpr (Diag::kQueueDry<kStats>) dg.queue_dry<kStats>();
                         break;
                     }
-#ifdef TRAY_PROFILE_TIMELINE
-                    tl_chunks += cnt;
-#endif
+                    if constexpr (Diag::kChunksTaken<kStats>) dg.chunks_taken(cnt);
                     grp_next = c + 1;
                     grp_end = c + cnt;
                 }
@@ -1071,19 +875,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             pool_next += take;
             idle = __ballot(!L.busy && fresh_item == ~0u);
         }
-#if defined(TRAY_PROFILE) && !defined(TRAY_PROFILE_REFILL)
-        {
-            const uint64_t fresh = __ballot(fresh_item != ~0u);
-            PROF_CNT(13, fresh != 0ull ? 1 : 0);
-            PROF_CNT(14, __popcll(fresh));
-#ifdef TRAY_PROFILE_BEGIN  // refills that find segments readied by the shade phase just before
-            if constexpr (kBVH) PROF_CNT(12, (uint64_t)(fresh != 0ull && __ballot(T.cur == kTravHit) != 0ull) << 40);
-#endif
-        }
-#endif
-#ifdef TRAY_PROFILE_REFILL
-        const uint64_t prof_assigned = __builtin_amdgcn_s_memtime();
-#endif
+        if constexpr (Diag::kRefillAssigned) dg.refill_assigned<kBVH>(lane, fresh_item != ~0u, T.cur);
         if (fresh_item != ~0u) {
             TRAY_MARK("refill_cam")
             const KernelParams& pr = kp_fresh();
@@ -1093,9 +885,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             if constexpr (!kChunkPixel)
                 valid = fresh_item < pr.items && decode_item(pr, fresh_item, fresh_tile, x, j, smp, pass);
             if (valid) {
-#ifdef TRAY_PROBE_REFILL
-                TRAY_PROBE_F32(TRAY_PROBE_REFILL)
-#endif
+                if constexpr (kProbed<kProbeRefill>) probe<kProbeRefill>();
                 // The pixel's primary-ray candidates, loaded before the camera ray is built.
                 uint4 cand = make_uint4(0u, 0u, 0u, kCandOverflow << 16);
                 if constexpr (kBVH)
@@ -1103,19 +893,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 start_sample(pr, L, fresh_item, x, j,
                              kChunkPixel ? fresh_sample + fresh_item : (pr.pass0 + pass) * (uint32_t)pr.spp + smp);
                 L.slot = kChunkPixel ? (uint32_t)fresh_xs >> kXsShift : fresh_slot;
-#ifdef TRAY_PROFILE_REFILL
-                prof_cam = __builtin_amdgcn_s_memtime();
-#endif
-#ifdef TRAY_STATS_GROUND
-                gcls = 0;
-#endif
-#ifdef TRAY_PROFILE_CANDWAIT
-                {  // diagnostic: the candidate record's exposed latency after the camera ray
-                    const uint64_t w0 = __builtin_amdgcn_s_memtime();
-                    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-                    prof_wait = __builtin_amdgcn_s_memtime() - w0 + 1u;
-                }
-#endif
+                if constexpr (Diag::kCameraRayBuilt<kStats>) dg.camera_ray_built();
                 if constexpr (kBVH) {
                     TRAY_MARK("refill_cand")
                     ++L.segments;
@@ -1147,21 +925,17 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                         trav_begin32(T, sv, L.org, L.dir);
                     }
                 }
-#ifdef TRAY_PROFILE_REFILL
-                prof_hit = __builtin_amdgcn_s_memtime();
-#endif
+                if constexpr (Diag::kCameraHitDone) dg.camera_hit_done();
             }
         }
-#ifdef TRAY_PROFILE_REFILL
-        const uint64_t prof_shade0 = __builtin_amdgcn_s_memtime();
-#endif
+        if constexpr (Diag::kCameraRaysDone) dg.camera_rays_done();
         // The refill's camera rays with a known hit are shaded at once (their
         // scattered rays join the node steps below) instead of waiting for the
         // shade batch; the traversal lanes' batching is unchanged. Here: the end half
         // (sky, last level); a hit that scatters is marked for the scatter step below.
         if constexpr (kBVH) {
             if (__ballot(cam_hit) != 0ull) {
-                PROF_T0E();
+                if constexpr (Diag::kEndHalf) dg.end_half_begin();
                 TRAY_MARK("refill_shade")
                 bool ended = false;
                 if (cam_hit) {
@@ -1171,50 +945,11 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                         ended = true;
                 }
                 if constexpr (kProg) count_progress(p, ended, L.j, lane, prog_cur, prog_cnt);
-#ifdef TRAY_PROFILE_BEGIN
-                {
-                    const uint64_t m = __ballot(T.cur == kTravHitCam);
-                    PROF_CNT(11, ((uint64_t)(m != 0ull) << 40) + (uint64_t)__popcll(m));
-                }
-#endif
-                PROF_ADDE(16);  // the refill's end half (also inside slot 0's refill time)
-                PROF_CNT(17, 1);
-                PROF_CNT(18, __popcll(__ballot(cam_hit)));
+                if constexpr (Diag::kEndHalf) dg.end_half_end(lane, T.cur, cam_hit);
             }
         }
-#ifdef TRAY_PROFILE_REFILL
-        {
-            const uint64_t prof_shade1 = __builtin_amdgcn_s_memtime();
-            PROF_CNT(10, prof_assigned - prof_t0_);  // item assignment (pool, queue)
-            PROF_CNT(15, prof_shade1 - prof_shade0);  // shading of the candidate-answered camera rays
-            const uint64_t mw = __ballot(prof_cam != 0u);
-            if (mw != 0ull) {
-                const uint32_t lw = (uint32_t)__builtin_ctzll(mw);
-                const uint64_t c = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(prof_cam >> 32), lw) << 32) |
-                                   (uint32_t)__builtin_amdgcn_readlane((uint32_t)prof_cam, lw);
-                const uint64_t h = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(prof_hit >> 32), lw) << 32) |
-                                   (uint32_t)__builtin_amdgcn_readlane((uint32_t)prof_hit, lw);
-                PROF_CNT(13, c - prof_assigned);  // decoding + camera ray (draw block, discs)
-                PROF_CNT(14, h - c);              // out-of-tree spheres + candidates (or the FP32 setup)
-            }
-        }
-#endif
-#ifdef TRAY_PROFILE_CANDWAIT
-        {
-            const uint64_t mw = __ballot(prof_wait != 0u);
-            if (mw != 0ull) {
-                const uint32_t lw = (uint32_t)__builtin_ctzll(mw);
-                const uint64_t w = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(prof_wait >> 32), lw) << 32) |
-                                   (uint32_t)__builtin_amdgcn_readlane((uint32_t)prof_wait, lw);
-                PROF_CNT(15, w - 1u);
-            }
-        }
-#endif
-        PROF_ADD(0);
+        if constexpr (Diag::kRefillDone<kStats>) dg.refill_done<kStats>(lane, L.busy);
         TRAY_MARK("refill_end")
-#ifdef TRAY_PROFILE_TIMELINE
-        tl_busy = (uint32_t)__popcll(__ballot(L.busy));
-#endif
         if (__ballot(L.busy) == 0ull) {
             if (exhausted) break;
             continue;              // every lane drew a padding item: draw again
@@ -1250,34 +985,17 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             // test above, which a marked lane fails (it is busy): the loop's exit, the
             // drain, the node steps, the leaf phase and the shade phase never see the state.
             if (__ballot(is_marked(T.cur)) != 0ull) {
-                PROF_T0();
+                if constexpr (Diag::kPhase<kStats>) dg.phase_begin<kStats>();
                 TRAY_MARK("scatter_ctl")
-                PROF_CNT(20, 1);
-                PROF_CNT(21, __popcll(__ballot(is_marked(T.cur))));
-#ifdef TRAY_PROFILE_BEGIN
-                PROF_CNT(12, __popcll(__ballot(is_marked(T.cur))));
-#endif
-                PROF_MATERIAL(0, T.cur == kTravHitCam);
-                PROF_MATERIAL(1, T.cur == kTravHit);
+                if constexpr (Diag::kScatterBegin) dg.scatter_begin(p, lane, T.cur, T.slot, L.bounce);
                 bool ended = false;
                 if (is_marked(T.cur)) {
                     TRAY_MARK("scatter")
-#if defined(TRAY_STATS_GROUND) && !defined(TRAY_PROFILE)
-                    const bool from_g = T.slot >= sv.global_first;
-#endif
                     if (shade_scatter<kStats, kAcc, false>(kp_fresh(), L, T.closest, T.a, [&] { return sv.bgeo[T.slot]; },
                                                            [&] { return sv.bmat[T.slot]; }, st, acc)) {
                         ++L.segments;
-#if defined(TRAY_STATS_GROUND) && !defined(TRAY_PROFILE)
-                        {
-                            const bool up = L.dir.y >= __builtin_fmax(__builtin_fabs(L.dir.x), __builtin_fabs(L.dir.z));
-                            gcls = from_g ? (up ? 1u : 2u) : 0u;
-                            if constexpr (kStats) {
-                                if (gcls == 1) ++st.g_seg[0];
-                                if (gcls != 0) ++st.g_seg[1];
-                            }
-                        }
-#endif
+                        if constexpr (Diag::kScatterSegment<kStats>)
+                            dg.scatter_segment<kStats>(T.slot >= sv.global_first, L.dir, st);
                         T.cur = kTravReady;  // set up by the begin part below
                     } else {
                         ended = true;  // absorbed: the lane is idle
@@ -1285,31 +1003,21 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                     }
                 }
                 if constexpr (kProg) count_progress(p, ended, L.j, lane, prog_cur, prog_cnt);
-                PROF_CNT(22, __popcll(__ballot(ended)));
-#ifdef TRAY_PROFILE
-                PROF_ADD(19);
-#else
-                PROF_ADD(3);  // the timeline build: counted with the shading
-#endif
+                if constexpr (Diag::kScatterEnd) dg.scatter_end(lane, ended);
+                if constexpr (Diag::kPhase<kStats>) dg.phase_end<kProfScatter, kStats>(lane);
                 TRAY_MARK("scatter_end")
             }
             // The begin part, in a block of its own: the compiler allocates the two apart
             // without the SGPR spill the product instance has with them in one.
             {
-                PROF_T0();
-#if defined(TRAY_PROFILE) && !defined(TRAY_PROFILE_REFILL) && !defined(TRAY_PROFILE_CANDWAIT)  // (they time into slot 15)
-                PROF_CNT(15, __ballot(T.cur == kTravReady) != 0ull ? 1 : 0);
-#endif
+                if constexpr (Diag::kPhase<kStats>) dg.phase_begin<kStats>();
+                if constexpr (Diag::kBeginPart) dg.begin_part(lane, T.cur);
                 if (T.cur == kTravReady) {
                     TRAY_MARK("begin")
                     trav_begin(T, sv, L.org, L.dir);
                     if constexpr (kStats) st.spheres += (uint64_t)sv.n_global;
                 }
-#ifdef TRAY_PROFILE
-                PROF_ADD(23);
-#else
-                PROF_ADD(0);  // the timeline build: counted with the refill
-#endif
+                if constexpr (Diag::kPhase<kStats>) dg.phase_end<kProfBegin, kStats>(lane);
                 TRAY_MARK("begin_end")
             }
             if constexpr (kLDS == 1) {
@@ -1318,20 +1026,20 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 if (exhausted) {
                     const KernelParams& pd = kp_fresh();
                     if (pd.coop_lanes != 0u && (uint32_t)__popcll(__ballot(L.busy)) <= pd.coop_lanes) {
-                        PROF_T0();
+                        if constexpr (Diag::kPhase<kStats>) dg.phase_begin<kStats>();
                         uint64_t m = __ballot(L.busy && T.cur != kBvhNone);
                         while (m != 0ull) {
                             const uint32_t l = (uint32_t)__builtin_ctzll(m);
                             m &= m - 1ull;
                             coop_hit(T, sv, pd.n_slots, L.org, L.dir, l, lane);
                         }
-                        PROF_ADD(1);
+                        if constexpr (Diag::kPhase<kStats>) dg.phase_end<kProfNode, kStats>(lane);
                     }
                 }
             }
             // Node steps for the traversing lanes.
             {
-                PROF_T0();
+                if constexpr (Diag::kPhase<kStats>) dg.phase_begin<kStats>();
                 TRAY_MARK("node_ctl")
                 // Unrolled: the steps are straight-line code (no loop counter, and the
                 // compiler schedules across them; C2 -0.9 %, C5 -0.8 % against a rolled loop).
@@ -1340,36 +1048,17 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                     const uint64_t m = __ballot(is_trav(T.cur));
                     if (m == 0ull) break;
                     if (s >= TRAY_NODE_STEPS && __popcll(m) < TRAY_NODE_MORE_LANES) break;
-                    PROF_CNT(4, 1);
-                    PROF_CNT(5, __popcll(m));
-#ifndef TRAY_PROFILE_BEGIN
-                    PROF_CNT(11, __popcll(__ballot(is_leaf(T.cur))));             // waiting for the leaf phase
-                    PROF_CNT(12, __popcll(__ballot(L.busy && T.cur == kBvhNone)));  // waiting for the shade phase
-#endif
+                    if constexpr (Diag::kNodeStep) dg.node_step(lane, m, T.cur, L.busy);
                     if (is_trav(T.cur)) {
                         TRAY_MARK("node")
                         uint32_t tested;
-#ifdef TRAY_PROBE_NODE
-                        TRAY_PROBE_F32(TRAY_PROBE_NODE)
-#endif
+                        if constexpr (kProbed<kProbeNode>) probe<kProbeNode>();
                         trav_node(T, sv, S, tested);
                         if constexpr (kStats) st.boxes += tested;
-#if defined(TRAY_STATS_PRIMARY) && !defined(TRAY_PROFILE)
-                        if constexpr (kStats) {
-                            ++st.nodes;
-                            if (L.bounce == 0) ++st.nodes0, st.boxes0 += tested;
-                        }
-#endif
-#if defined(TRAY_STATS_GROUND) && !defined(TRAY_PROFILE)
-                        if constexpr (kStats) {
-                            ++st.nodes;
-                            if (gcls == 1) ++st.g_nodes[0];
-                            if (gcls != 0) ++st.g_nodes[1];
-                        }
-#endif
+                        if constexpr (Diag::kNodeVisit<kStats>) dg.node_visit<kStats>(st, tested, L.bounce);
                     }
                 }
-                PROF_ADD(1);
+                if constexpr (Diag::kPhase<kStats>) dg.phase_end<kProfNode, kStats>(lane);
                 TRAY_MARK("leaf_decide")
             }
             // Leaf phase: FP64 sphere tests, batched.
@@ -1377,34 +1066,19 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             const uint32_t n_trav = (uint32_t)__popcll(__ballot(is_trav(T.cur)));
             if (m_leaf != 0ull && (__popcll(m_leaf) >= TRAY_LEAF_BATCH || n_trav == 0u ||
                                    (n_trav < TRAY_TRAV_SPARSE && __popcll(m_leaf) >= TRAY_LEAF_LOW))) {
-                PROF_T0();
+                if constexpr (Diag::kPhase<kStats>) dg.phase_begin<kStats>();
                 TRAY_MARK("leaf_ctl")
-                PROF_CNT(6, 1);
-                PROF_CNT(7, __popcll(m_leaf));
+                if constexpr (Diag::kLeafPhase) dg.leaf_phase(lane, m_leaf);
                 __builtin_amdgcn_s_setprio(1);
                 if (is_leaf(T.cur)) {
                     TRAY_MARK("leaf")
                     uint32_t tested;
-#ifdef TRAY_PROBE_LEAF
-                    TRAY_PROBE_F32(TRAY_PROBE_LEAF)
-#endif
+                    if constexpr (kProbed<kProbeLeaf>) probe<kProbeLeaf>();
                     trav_leaf(T, sv, S, L.org, L.dir, tested);
                     if constexpr (kStats) st.spheres += tested;
-#if defined(TRAY_STATS_PRIMARY) && !defined(TRAY_PROFILE)
-                    if constexpr (kStats) {
-                        ++st.leaves;
-                        if (L.bounce == 0) ++st.leaves0;
-                    }
-#endif
-#if defined(TRAY_STATS_GROUND) && !defined(TRAY_PROFILE)
-                    if constexpr (kStats) {
-                        ++st.leaves;
-                        if (gcls == 1) ++st.g_leaves[0];
-                        if (gcls != 0) ++st.g_leaves[1];
-                    }
-#endif
+                    if constexpr (Diag::kLeafVisit<kStats>) dg.leaf_visit<kStats>(st, L.bounce);
                 }
-                PROF_ADD(2);
+                if constexpr (Diag::kPhase<kStats>) dg.phase_end<kProfLeaf, kStats>(lane);
                 __builtin_amdgcn_s_setprio(0);
             }
             // Shading phase, batched.
@@ -1412,19 +1086,14 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             if (m_shade != 0ull && (__popcll(m_shade) >= TRAY_SHADE_BATCH || __ballot(T.cur < kBvhNone) == 0ull ||
                                     (__popcll(__ballot(is_trav(T.cur))) < TRAY_TRAV_SPARSE &&
                                      __popcll(m_shade) >= TRAY_SHADE_LOW))) {
-                PROF_T0();
+                if constexpr (Diag::kPhase<kStats>) dg.phase_begin<kStats>();
                 TRAY_MARK("shade_ctl")
-                PROF_CNT(8, 1);
-                PROF_CNT(9, __popcll(m_shade));
+                if constexpr (Diag::kShadePhase) dg.shade_phase(lane, m_shade);
                 bool ended = false;
                 if (L.busy && T.cur == kBvhNone) {
                     TRAY_MARK("shade")
-#ifdef TRAY_PROBE_SHADE
-                    TRAY_PROBE_F32(TRAY_PROBE_SHADE)
-#endif
-#ifdef TRAY_PROBE_SHADE64
-                    TRAY_PROBE_F64(TRAY_PROBE_SHADE64)
-#endif
+                    if constexpr (kProbed<kProbeShade>) probe<kProbeShade>();
+                    if constexpr (kProbed<kProbeShade64>) probe<kProbeShade64>();
                     // The end half (sky, last level); a hit that scatters is marked for the
                     // scatter step of the next iteration.
                     if (shade_end<kStats, kAcc, false>(kp_fresh(), L, T.slot >= 0, T.a, st, acc))
@@ -1433,13 +1102,8 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                         ended = true;  // idle: T.cur stays kBvhNone, L.busy is false
                 }
                 if constexpr (kProg) count_progress(p, ended, L.j, lane, prog_cur, prog_cnt);
-#ifdef TRAY_PROFILE_BEGIN
-                {
-                    const uint64_t m = __ballot(T.cur == kTravHit);
-                    PROF_CNT(10, ((uint64_t)(m != 0ull) << 40) + (uint64_t)__popcll(m));
-                }
-#endif
-                PROF_ADD(3);
+                if constexpr (Diag::kShadeMarked) dg.shade_marked(lane, T.cur);
+                if constexpr (Diag::kPhase<kStats>) dg.phase_end<kProfShade, kStats>(lane);
                 TRAY_MARK("shade_end")
             }
         }
@@ -1457,53 +1121,8 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             atomicAdd(p.stats + 1, (unsigned long long)sph_w);
             atomicAdd(p.stats + 2, (unsigned long long)box_w);
         }
-#if defined(TRAY_STATS_PRIMARY) && !defined(TRAY_PROFILE)
-        atomicAdd(p.stats + 3, (unsigned long long)st.nodes0);
-        atomicAdd(p.stats + 4, (unsigned long long)st.leaves0);
-        atomicAdd(p.stats + 5, (unsigned long long)st.boxes0);
-        atomicAdd(p.stats + 6, (unsigned long long)st.nodes);
-        atomicAdd(p.stats + 7, (unsigned long long)st.leaves);
-#endif
-#if defined(TRAY_STATS_GROUND) && !defined(TRAY_PROFILE)
-        for (int k = 0; k < 2; ++k) {
-            atomicAdd(p.stats + 3 + k, (unsigned long long)st.g_seg[k]);
-            atomicAdd(p.stats + 5 + k, (unsigned long long)st.g_nodes[k]);
-            atomicAdd(p.stats + 7 + k, (unsigned long long)st.g_leaves[k]);
-        }
-        atomicAdd(p.stats + 9, (unsigned long long)st.nodes);
-        atomicAdd(p.stats + 10, (unsigned long long)st.leaves);
-#endif
     }
-#ifdef TRAY_PROFILE_TIMELINE
-    if (kStats && lane == 0) {
-        const uint64_t end = __builtin_amdgcn_s_memrealtime();
-        const uint64_t mt_end = __builtin_amdgcn_s_memtime();
-        tl_acc += (mt_end - tl_prev) * tl_busy;
-        tl[kTlHdr + tl_bucket] = tl_acc;
-        for (int k = 0; k < 4; ++k) tl[kTlHdr + kTlBuckets - 9 + k] = tl_ph[k];
-        tl[0] = tl_start;
-        tl[1] = end;
-        tl[2] = tl_dry;
-        tl[3] = tl_chunks;
-        tl[4] = tl_mt0;
-        tl[5] = mt_end;
-    }
-#endif
-#ifdef TRAY_PROFILE
-    if (kStats && lane == 0) {
-        for (int i = 0; i < 16; ++i) atomicAdd(p.stats + 3 + i, (unsigned long long)prof[i]);
-        for (int i = 16; i < 24; ++i) atomicAdd(p.stats + 6 + i, (unsigned long long)prof[i]);
-        // Wave lifetimes on the constant-rate clock: latest exit, sum of lifetimes, earliest start.
-        const uint64_t end = __builtin_amdgcn_s_memrealtime();
-        atomicMax(p.stats + 19, (unsigned long long)end);
-        atomicAdd(p.stats + 20, (unsigned long long)(end - prof_start));
-        atomicMax(p.stats + 21, (unsigned long long)~prof_start);
-        // Per-wave (start, end) from stats[32] on (the buffer must hold 32 + 2 x waves).
-        const uint32_t wave = blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u;
-        p.stats[32 + 2 * wave] = prof_start;
-        p.stats[33 + 2 * wave] = end;
-    }
-#endif
+    if constexpr (Diag::kKernelEnd<kStats>) dg.kernel_end<kStats>(p, st, lane);
 }
 
 // A band's pixels: the mean of each pixel's samples, added in sample order
