@@ -407,6 +407,7 @@ __device__ __forceinline__ uint64_t acc_retire(const KernelParams& p, const AccC
     // issue order, so the reads see every addition its lanes made.
     // Each of the slot's groups (one per chunk, or 64 / r pixel-passes) is one record.
     if ((freed >> lane) & 1ull) {
+        asm volatile("" : "+v"(lane));
         const uint32_t groups = 64u >> acc_rshift<kAcc>(p);
         // the chunk's Scene.Hit calls (a counting launch; 0 otherwise) ride in group 0's pad
         uint32_t count = 0u;
@@ -730,11 +731,12 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
         LdsF64* all = (LdsF64*)reinterpret_cast<double*>(reinterpret_cast<char*>(smem_all) + p.acc_off);
         const uint32_t waves = blockDim.x / 64u, slot_f64 = (64u >> acc_rshift<kAcc>(p)) * kAccCopies * 3u;
         const uint32_t slots = (uint32_t)p.acc_slots;
+        const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64u);  // the wave's bases are scalars
         for (uint32_t i = threadIdx.x; i < waves * slots * slot_f64; i += blockDim.x) all[i] = 0.0;
-        acc.slabs = all + (threadIdx.x / 64u) * slots * slot_f64;
+        acc.slabs = all + wave * slots * slot_f64;
         LdsU32* counts = (LdsU32*)(all + waves * slots * slot_f64);
         for (uint32_t i = threadIdx.x; i < waves * slots; i += blockDim.x) counts[i] = 0u;
-        acc.counts = counts + (threadIdx.x / 64u) * slots;
+        acc.counts = counts + wave * slots;
         acc_free = acc_all_slots(p);
     }
     __syncthreads();
@@ -765,6 +767,15 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
     static_assert(kAccSlotsMax <= 64, "pool_xs: x | slot << 24 stays non-negative");
     int32_t pool_xs = -1, pool_j = 0;
     uint32_t pool_sample = 0;
+    // The first chunk of the run of the pixel decoded last (the refill's take). kNoRun: none, and no
+    // chunk of a band (< 2^25) is within a run's length (<= 2^25) of it.
+#ifdef TRAY_AB_DECODE_EVERY_TAKE  // A/B only: every take decodes its chunk
+    constexpr bool kRunDecode = false;
+#else
+    constexpr bool kRunDecode = kChunkPixel;
+#endif
+    constexpr uint32_t kNoRun = 0x80000000u;
+    uint32_t run_first = kNoRun;
     bool exhausted = false;
     int32_t prog_cur = 0;  // live progress: the wave's current tile row and its unflushed count
     uint64_t prog_cnt = 0;
@@ -782,12 +793,47 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
         if (__popcll(idle) < TRAY_REFILL_BATCH && idle != ~0ull) idle = 0ull;  // batch refills
         // Items are assigned first (cheap, may span two chunks); the camera rays of
         // all newly assigned lanes are then generated together.
-        uint32_t fresh_item = ~0u, fresh_slot = 0u, fresh_tile = 0u;
-        int32_t fresh_xs = -1, fresh_j = 0;  // kChunkPixel: the lane's copy of its chunk's pixel and slot
-        uint32_t fresh_sample = 0u;
+        // A lane's item and its copy of the chunk's values go straight into its Lane fields, dead
+        // while it idles: item and slot; kChunkPixel: column, compact row and the sample word less
+        // the item; otherwise the chunk's tile, in L.x until the lane's decode.
+        bool fresh = false;       // the lane was given an item in this refill
+        bool fresh_real = false;  // kChunkPixel: and its chunk is no padding (it holds a slot)
         bool cam_hit = false;  // a camera ray whose Scene.Hit the candidate list answered in this refill
+#ifdef TRAY_AB_ASSIGN_LOOP  // A/B only: the loop this replaced, a trip per chunk, the still-idle lanes ranked in each
         while (idle != 0ull && !exhausted) {
             if (pool_next == pool_end) {
+#else
+        // At most 64 lanes are idle and a chunk has 64 items: the idle lanes take the rest of the
+        // current chunk, then - after the one take there can be, and only if it yields a chunk -
+        // the lanes still idle take the first items of the next. Nothing but the lanes' copies
+        // lives across the take: the second ranks come from a ballot behind it. No loop, and no
+        // lambda for the parts either: each costs the BVH instances registers.
+        if (idle != 0ull && !exhausted) do {
+            // Before the take overwrites the chunk's values: a lane copies them here.
+            const uint32_t n_idle = (uint32_t)__popcll(idle);
+            const uint32_t rest = min(n_idle, pool_end - pool_next);
+            if ((idle >> lane) & 1ull) {
+                const uint32_t rank =  // idle lanes below this one
+                    __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (rank < rest) {
+                    fresh = true;
+                    L.item = pool_next + rank;
+                    if constexpr (kChunkPixel) {
+                        fresh_real = pool_xs >= 0;
+                        L.x = pool_xs & (int32_t)((1u << kXsShift) - 1u);
+                        L.slot = (uint32_t)pool_xs >> kXsShift;
+                        L.j = pool_j;
+                        L.sample = pool_sample;
+                    } else {
+                        L.x = (int32_t)pool_tile;
+                        L.slot = pool_slot;
+                    }
+                }
+            }
+            pool_next += rest;
+            if (n_idle == rest) break;
+            {  // the current chunk is used up: the next one (a `break`: none now, the lanes above go on alone)
+#endif
                 if constexpr (kAcc) {
                     // A chunk needs a free accumulator: with none, the idle lanes wait
                     // for one of the wave's open chunks to finish (every open chunk
@@ -796,14 +842,13 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                         // Retire the chunks no busy lane traces any more (lanes assigned in
                         // this refill have not started yet: their chunk is open regardless).
                         // (kChunkPixel: a lane given an item of a padding chunk holds no slot.)
-                        const bool held = L.busy || (kChunkPixel ? fresh_xs >= 0 : fresh_item != ~0u);
-                        const uint32_t fresh_held = kChunkPixel ? (uint32_t)fresh_xs >> kXsShift : fresh_slot;
-                        acc_free = acc_retire<kAcc>(kp_fresh(), acc, acc_all_slots(kp_fresh()), held,
-                                                    L.busy ? L.slot : fresh_held, acc_chunk, lane);
+                        const bool held = L.busy || (kChunkPixel ? fresh_real : fresh);
+                        acc_free = acc_retire<kAcc>(kp_fresh(), acc, acc_all_slots(kp_fresh()), held, L.slot, acc_chunk,
+                                                    lane);
                     }
                     if (acc_free == 0ull) {
                         // unreachable with nothing in flight: no chunk would hold a slot
-                        if (__ballot(L.busy || fresh_item != ~0u) == 0ull) __builtin_trap();
+                        if (__ballot(L.busy || fresh) == 0ull) __builtin_trap();
                         break;
                     }
                 }
@@ -826,34 +871,51 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 pool_next = c * 64u;
                 pool_end = pool_next + 64u;
                 const KernelParams& pc = kp_fresh();
-                pool_tile = chunk_tile(pc, c);
                 if constexpr (kChunkPixel) {
                     // Every item of the chunk is one pixel's: valid or padding together, and a
-                    // padding chunk takes no slot.
-                    int32_t cx;
-                    uint32_t cs, cp;
-                    pool_xs = -1;
-                    if (pool_next < pc.items && decode_item(pc, pool_next, pool_tile, cx, pool_j, cs, cp)) {
-                        pool_sample = (pc.pass0 + cp) * (uint32_t)pc.spp + cs - pool_next;
+                    // padding chunk takes no slot. So are the items of the pixel's other chunks, the
+                    // run of passes x r / 64 chunks around this one: a take inside the run of the last
+                    // decode keeps the column, the row, the sample word's offset and the padding
+                    // verdict, and only takes a slot (a wave's takes need not be consecutive).
+                    bool decode = true;
+                    if constexpr (kRunDecode) decode = c - run_first >= (pc.div_chunks_per_tile.d >> 6);
+                    if (decode) {
+                        int32_t cx;
+                        uint32_t cs, cp;
+                        pool_xs = -1;
+                        run_first = kNoRun;
+                        if (pool_next < pc.items) {
+                            if (decode_item(pc, pool_next, chunk_tile(pc, c), cx, pool_j, cs, cp)) {
+                                pool_sample = (pc.pass0 + cp) * (uint32_t)pc.spp + cs - pool_next;
+                                pool_xs = cx;
+                            }
+                            if constexpr (kRunDecode) run_first = c - (cp * ((uint32_t)pc.spp >> 6) + (cs >> 6));
+                        }
+                    }
+                    if (pool_xs >= 0) {
                         const uint32_t slot = (uint32_t)__builtin_ctzll(acc_free);
                         acc_free &= ~(1ull << slot);
                         acc_chunk = lane == slot ? c : acc_chunk;
-                        pool_xs = cx | (int32_t)(slot << kXsShift);
+                        pool_xs = (pool_xs & (int32_t)((1u << kXsShift) - 1u)) | (int32_t)(slot << kXsShift);
                     }
-                } else if constexpr (kAcc) {
-                    // With 64 | r every item of a chunk is one pixel's: valid or padding
-                    // together. A chunk of several pixel-passes (r | 64) may mix the two
-                    // and always takes a slot (its padding groups retire as zeros).
-                    int32_t cx, cj;
-                    uint32_t cs, cp;
-                    if (acc_rshift<kAcc>(p) < 6u ||
-                        (pool_next < pc.items && decode_item(pc, pool_next, pool_tile, cx, cj, cs, cp))) {
-                        pool_slot = (uint32_t)__builtin_ctzll(acc_free);
-                        acc_free &= ~(1ull << pool_slot);
-                        acc_chunk = lane == pool_slot ? c : acc_chunk;
+                } else {
+                    pool_tile = chunk_tile(pc, c);
+                    if constexpr (kAcc) {
+                        // With 64 | r every item of a chunk is one pixel's: valid or padding
+                        // together. A chunk of several pixel-passes (r | 64) may mix the two
+                        // and always takes a slot (its padding groups retire as zeros).
+                        int32_t cx, cj;
+                        uint32_t cs, cp;
+                        if (acc_rshift<kAcc>(p) < 6u ||
+                            (pool_next < pc.items && decode_item(pc, pool_next, pool_tile, cx, cj, cs, cp))) {
+                            pool_slot = (uint32_t)__builtin_ctzll(acc_free);
+                            acc_free &= ~(1ull << pool_slot);
+                            acc_chunk = lane == pool_slot ? c : acc_chunk;
+                        }
                     }
                 }
             }
+#ifdef TRAY_AB_ASSIGN_LOOP
             const uint32_t n_idle = (uint32_t)__popcll(idle);
             const uint32_t take = min(n_idle, pool_end - pool_next);
             if ((idle >> lane) & 1ull) {
@@ -861,38 +923,60 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 const uint32_t rank =
                     __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
                 if (rank < take) {
-                    fresh_item = pool_next + rank;
+                    fresh = true;
+                    L.item = pool_next + rank;
                     if constexpr (kChunkPixel) {
-                        fresh_xs = pool_xs;
-                        fresh_j = pool_j;
-                        fresh_sample = pool_sample;
+                        fresh_real = pool_xs >= 0;
+                        L.x = pool_xs & (int32_t)((1u << kXsShift) - 1u);
+                        L.slot = (uint32_t)pool_xs >> kXsShift;
+                        L.j = pool_j;
+                        L.sample = pool_sample;
                     } else {
-                        fresh_slot = pool_slot;
-                        fresh_tile = pool_tile;
+                        L.x = (int32_t)pool_tile;
+                        L.slot = pool_slot;
                     }
                 }
             }
             pool_next += take;
-            idle = __ballot(!L.busy && fresh_item == ~0u);
+            idle = __ballot(!L.busy && !fresh);
         }
-        if constexpr (Diag::kRefillAssigned) dg.refill_assigned<kBVH>(lane, fresh_item != ~0u, T.cur);
-        if (fresh_item != ~0u) {
+#else
+            idle = __ballot(!L.busy && !fresh);  // the lanes the current chunk's rest left idle
+            if ((idle >> lane) & 1ull) {
+                fresh = true;
+                L.item = pool_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32),
+                                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if constexpr (kChunkPixel) {
+                    fresh_real = pool_xs >= 0;
+                    L.x = pool_xs & (int32_t)((1u << kXsShift) - 1u);
+                    L.slot = (uint32_t)pool_xs >> kXsShift;
+                    L.j = pool_j;
+                    L.sample = pool_sample;
+                } else {
+                    L.x = (int32_t)pool_tile;
+                    L.slot = pool_slot;
+                }
+            }
+            pool_next += (uint32_t)__popcll(idle);
+        } while (false);
+#endif
+        if constexpr (Diag::kRefillAssigned) dg.refill_assigned<kBVH>(lane, fresh, T.cur);
+        if (fresh) {
             TRAY_MARK("refill_cam")
             const KernelParams& pr = kp_fresh();
-            int32_t x = fresh_xs & (int32_t)((1u << kXsShift) - 1u), j = fresh_j;
+            int32_t x = L.x, j = L.j;
             uint32_t smp = 0, pass = 0;
-            bool valid = fresh_xs >= 0;  // kChunkPixel: the chunk's decode
+            bool valid = fresh_real;  // kChunkPixel: the chunk's decode
             if constexpr (!kChunkPixel)
-                valid = fresh_item < pr.items && decode_item(pr, fresh_item, fresh_tile, x, j, smp, pass);
+                valid = L.item < pr.items && decode_item(pr, L.item, (uint32_t)L.x, x, j, smp, pass);
             if (valid) {
                 if constexpr (kProbed<kProbeRefill>) probe<kProbeRefill>();
                 // The pixel's primary-ray candidates, loaded before the camera ray is built.
                 uint4 cand = make_uint4(0u, 0u, 0u, kCandOverflow << 16);
                 if constexpr (kBVH)
                     if (pr.cand) cand = pr.cand[(size_t)j * (size_t)pr.width + (size_t)x];
-                start_sample(pr, L, fresh_item, x, j,
-                             kChunkPixel ? fresh_sample + fresh_item : (pr.pass0 + pass) * (uint32_t)pr.spp + smp);
-                L.slot = kChunkPixel ? (uint32_t)fresh_xs >> kXsShift : fresh_slot;
+                start_sample(pr, L, L.item, x, j,
+                             kChunkPixel ? L.sample + L.item : (pr.pass0 + pass) * (uint32_t)pr.spp + smp);
                 if constexpr (Diag::kCameraRayBuilt<kStats>) dg.camera_ray_built();
                 if constexpr (kBVH) {
                     TRAY_MARK("refill_cand")
