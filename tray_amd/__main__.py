@@ -10,6 +10,8 @@ have no meaning here).
                                           # the frame has converged (include/tray_progressive.h)
     python -m tray_amd -r 16 -passes 64 -adaptive [-denoise] ...  # the same, rendering only the pixels
                                           # that have not converged yet (include/tray_adaptive.h)
+    python -m tray_amd -r 4 -orbit 8 [-orbit-step DEG] [-denoise] ...  # a camera orbit that reuses each
+                                          # last frame by temporal reprojection (include/tray_temporal.h)
 """
 from __future__ import annotations
 
@@ -61,6 +63,12 @@ def main(argv=None) -> int:
     ap.add_argument("-adaptive", action="store_true",
                     help="with -passes: render only the unconverged pixels after a uniform warm-up "
                          "(include/tray_adaptive.h); prints the pixel-passes spent against h x w x passes")
+    ap.add_argument("-orbit", type=int, default=0, metavar="N",
+                    help="render N frames turning the camera about LookAt around the up axis, each reusing the "
+                         "last through temporal reprojection (include/tray_temporal.h); prints the fresh fraction "
+                         "and the mean age per frame and saves the last frame; -denoise applies")
+    ap.add_argument("-orbit-step", type=float, default=ray.ORBIT_STEP_DEGREES, metavar="DEG", dest="orbit_step",
+                    help="with -orbit: degrees between frames")
     ap.add_argument("-ansi", action="store_true",
                     help="render at -s x the terminal size and draw it in the terminal (main.go:86-131)")
     ap.add_argument("-s", type=float, default=4, help="supersampling factor of -ansi")
@@ -73,7 +81,15 @@ def main(argv=None) -> int:
     scene = ray.RichScene(a.seed)
     t0 = time.perf_counter()
     samples = a.width * a.height * a.r
-    if a.adaptive:
+    if a.orbit < 0 or (a.orbit and (a.passes or a.adaptive)):
+        ap.error("-orbit needs N >= 1 and goes with neither -passes nor -adaptive")
+    if a.orbit:
+        cameras = [ray.Orbit(t.Camera, k * a.orbit_step) for k in range(a.orbit)]
+        img = t.RenderSequence(scene, cameras, denoise=a.denoise)[-1]
+        for k, (fresh, age) in enumerate(zip(t.fresh, t.mean_age)):
+            print(f"frame {k}: fresh {fresh / max(a.width * a.height, 1):.4f} mean age {age:.3f}")
+        samples *= a.orbit
+    elif a.adaptive:
         if a.passes <= 0:
             ap.error("-adaptive needs -passes N")
         img = t.RenderAdaptive(scene, a.passes, tolerance=a.tolerance, denoise=a.denoise)

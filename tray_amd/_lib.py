@@ -329,6 +329,37 @@ ADAPTIVE_RECORD_DTYPE = np.dtype([("n_active", "<u8"), ("unconverged", "<u8"), (
 assert ctypes.sizeof(AdaptiveState) == 32 and ctypes.sizeof(AdaptiveParams) == 32
 assert ctypes.sizeof(AdaptiveRecord) == 32 and ADAPTIVE_RECORD_DTYPE.itemsize == 32
 
+# Every symbol include/tray_temporal.h declares (the temporal reprojection step; in none of the
+# seven lists above).
+TEMPORAL_EXPORTS = (
+    "tray_temporal_version",
+    "tray_temporal_default_params",
+    "tray_temporal_step_async",
+)
+
+
+class TemporalState(ctypes.Structure):
+    """tray_temporal_state: the device planes (colour, age, index, depth) of a width x height frame."""
+    _fields_ = [("colour", ctypes.c_void_p), ("age", ctypes.c_void_p), ("index", ctypes.c_void_p),
+                ("depth", ctypes.c_void_p), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
+class TemporalParams(ctypes.Structure):
+    """tray_temporal_params."""
+    _fields_ = [("max_history", ctypes.c_int32), ("flags", ctypes.c_int32), ("depth_tolerance", ctypes.c_double),
+                ("snap", ctypes.c_double), ("reserved", ctypes.c_int64)]
+
+
+class TemporalRecord(ctypes.Structure):
+    """tray_temporal_record: the 16-byte device record."""
+    _fields_ = [("fresh", ctypes.c_uint64), ("age_sum", ctypes.c_uint64)]
+
+
+# tray_temporal_record as a numpy structured dtype, for reading the record back.
+TEMPORAL_RECORD_DTYPE = np.dtype([("fresh", "<u8"), ("age_sum", "<u8")])
+assert ctypes.sizeof(TemporalState) == 40 and ctypes.sizeof(TemporalParams) == 32
+assert ctypes.sizeof(TemporalRecord) == 16 and TEMPORAL_RECORD_DTYPE.itemsize == 16
+
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
 DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear", "tray_debug_progress_counts")
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
@@ -450,6 +481,12 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.tray_adaptive_workspace_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
         L.tray_adaptive_select_async.argtypes = [ctypes.POINTER(AdaptiveState), ctypes.POINTER(AdaptiveParams), vp, vp,
                                                  vp, vp, ctypes.c_size_t, i32, vp]
+    if hasattr(L, "tray_temporal_version"):  # include/tray_temporal.h; absent from older builds (A/B tools)
+        L.tray_temporal_version.restype = i32
+        L.tray_temporal_default_params.argtypes = [ctypes.POINTER(TemporalParams)]
+        L.tray_temporal_step_async.argtypes = [vp, ctypes.POINTER(CameraState), ctypes.POINTER(CameraState),
+                                               ctypes.POINTER(TemporalParams), vp, ctypes.POINTER(TemporalState),
+                                               ctypes.POINTER(TemporalState), vp, vp]
     if hasattr(L, "tray_debug_set"):  # absent from older builds (A/B tools)
         L.tray_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
         L.tray_debug_clear.argtypes = [ctypes.c_char_p]
@@ -817,6 +854,34 @@ def adaptive_select_async(state: AdaptiveState, params: AdaptiveParams, pixels_p
     L = lib(lib_path)
     _raise(L, L.tray_adaptive_select_async(ctypes.byref(state), ctypes.byref(params), variance_ptr, pixels_ptr,
                                            record_ptr, workspace_ptr, int(workspace_bytes), int(device), stream))
+
+
+def temporal_params(lib_path: str | None = None, **overrides) -> TemporalParams:
+    """tray_temporal_default_params, with fields overridden by name."""
+    p = TemporalParams()
+    L = lib(lib_path)
+    _raise(L, L.tray_temporal_default_params(ctypes.byref(p)))
+    for name, value in overrides.items():
+        if name not in dict(TemporalParams._fields_):
+            raise ValueError(f"unknown temporal parameter {name!r}")
+        setattr(p, name, value)
+    return p
+
+
+def temporal_step_async(scene_handle: int | None, camera: CameraState | None, prev_camera: CameraState | None,
+                        params: TemporalParams, frame_ptr: int | None, history: TemporalState | None,
+                        out: TemporalState, record_ptr: int | None = None, stream: int | None = None,
+                        lib_path: str | None = None) -> None:
+    """tray_temporal_step_async on an uploaded scene's handle: reprojects `history` (a frame of
+    prev_camera; both None: the first frame) into `camera`, folds the new frame (height x width x 3
+    f64) into it and writes `out` and the 16-byte record (TEMPORAL_RECORD_DTYPE). Only enqueues
+    on `stream`."""
+    L = lib(lib_path)
+    _raise(L, L.tray_temporal_step_async(scene_handle, ctypes.byref(camera) if camera is not None else None,
+                                         ctypes.byref(prev_camera) if prev_camera is not None else None,
+                                         ctypes.byref(params), frame_ptr,
+                                         ctypes.byref(history) if history is not None else None, ctypes.byref(out),
+                                         record_ptr, stream))
 
 
 def camera_rays_count(params: Params) -> int:

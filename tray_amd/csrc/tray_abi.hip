@@ -1094,6 +1094,96 @@ int tray_render_pixels_async(tray_scene_t sc, const tray_camera* cam, const tray
     return TRAY_OK;
 }
 
+// ---- temporal reprojection (include/tray_temporal.h) -----------------------------
+int32_t tray_temporal_version(void) { return TRAY_TEMPORAL_VERSION; }
+
+int tray_temporal_default_params(tray_temporal_params* out) {
+    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params (out)");
+    out->max_history = 32;       // tools/temporal_sweep.py, DESIGN.md 8q
+    out->flags = 0;
+    out->depth_tolerance = 0.1;  // the same sweep
+    out->snap = 0x1.0p-20;
+    out->reserved = 0;
+    return TRAY_OK;
+}
+
+namespace {
+struct TemporalSpan {
+    const void* p;
+    size_t bytes;
+    uintptr_t align;
+    const char* name;
+};
+bool spans_overlap(const TemporalSpan& a, const TemporalSpan& b) {
+    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+    return a.p && b.p && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+}  // namespace
+
+int tray_temporal_step_async(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
+                             const tray_temporal_params* tp, const double* frame_device,
+                             const tray_temporal_state* history, const tray_temporal_state* out,
+                             tray_temporal_record* record_device, void* stream) {
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
+    if (!tp) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params");
+    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null state (out)");
+    if ((history == nullptr) != (prev == nullptr))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "history and prev_camera must both be given or both be null");
+    if (out->width < 0 || out->height < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative width or height");
+    if (history && (history->width != out->width || history->height != out->height))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "history and out differ in width or height");
+    if (tp->max_history < 1 || tp->max_history > (1 << 30))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "max_history must be in 1 .. 2^30");
+    if (tp->flags & ~TRAY_FLAG_LINEAR_SCAN)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "unknown flags (only TRAY_FLAG_LINEAR_SCAN applies)");
+    if (!(std::isfinite(tp->depth_tolerance) && tp->depth_tolerance >= 0.0))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "depth_tolerance must be finite and >= 0");
+    if (!(std::isfinite(tp->snap) && tp->snap >= 0.0 && tp->snap < 0.5))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "snap must be finite, >= 0 and < 0.5");
+    if (tp->reserved != 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "reserved must be 0");
+    const int64_t image = (int64_t)out->width * (int64_t)out->height;
+    if (image > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
+    if (image == 0) return TRAY_OK;
+    // The spans: outputs first (the first n_out), then what is only read.
+    const size_t px = (size_t)image;
+    TemporalSpan spans[10] = {{out->colour, px * 24, 8, "out.colour"},
+                              {out->age, px * 4, 4, "out.age"},
+                              {out->index, px * 4, 4, "out.index"},
+                              {out->depth, px * 8, 8, "out.depth"},
+                              {record_device, sizeof(tray_temporal_record), 8, "the record"},
+                              {frame_device, px * 24, 8, "the frame"}};
+    const int n_out = 5;
+    int n = 6;
+    if (history) {
+        spans[n++] = {history->colour, px * 24, 8, "history.colour"};
+        spans[n++] = {history->age, px * 4, 4, "history.age"};
+        spans[n++] = {history->index, px * 4, 4, "history.index"};
+        spans[n++] = {history->depth, px * 8, 8, "history.depth"};
+    }
+    for (int i = 0; i < n; ++i)
+        if (!spans[i].p && i != 4) return fail(TRAY_ERR_INVALID_ARGUMENT, std::string("null buffer: ") + spans[i].name);
+    for (int i = 0; i < n; ++i)
+        if ((uintptr_t)spans[i].p & (spans[i].align - 1))
+            return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(spans[i].name) + " is not " +
+                                                       (spans[i].align == 8 ? "8" : "4") + "-byte aligned");
+    for (int i = 0; i < n_out; ++i)
+        for (int j = i + 1; j < n; ++j)
+            if (spans_overlap(spans[i], spans[j]))
+                return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(spans[i].name) + " overlaps " + spans[j].name);
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    camera_params(cam, k);
+    k.width = out->width;
+    k.height = out->height;
+    k.rows = out->height;
+    TRAY_HIP(hipSetDevice(sc->device));
+    TRAY_HIP(launch_temporal_step(k, wants_bvh(sc, tp->flags), sc->bvh_bound, prev, *tp, frame_device, history, *out,
+                                  record_device, static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
 // The scene of a slot: its cached upload when the caller passes the same
 // spheres and background as last time (compared byte for byte; the caller's
 // arrays are copied, never retained), else a fresh upload that replaces it.

@@ -1,7 +1,8 @@
 // Internal launch interface between the C-ABI glue (tray_abi.hip) and the
 // ray-query kernels (tray_query.hip: include/tray_query.h, tray_shade.h and
-// tray_aov.h) and the pixel-list renderer (tray_adaptive.hip). Host side only:
-// the device functions those two units share are tray_query_device.hpp, over
+// tray_aov.h), the pixel-list renderer (tray_adaptive.hip) and the temporal
+// step (tray_temporal.hip). Host side only:
+// the device functions those units share are tray_query_device.hpp, over
 // tray_device.hpp, which the megakernel (tray_kernel.hip) compiles too.
 // Not part of the public ABI.
 #pragma once
@@ -11,6 +12,7 @@
 
 #include "../../include/tray_aov.h"
 #include "../../include/tray_shade.h"  // includes tray_query.h
+#include "../../include/tray_temporal.h"
 #include "tray_kernel.hpp"
 
 namespace tray {
@@ -65,5 +67,14 @@ hipError_t launch_render_aov(KernelParams p, bool use_bvh, double bound, const t
 hipError_t launch_render_pixels(KernelParams p, bool use_bvh, double bound, const uint32_t* pixels, uint32_t n_pixels,
                                 const int32_t* pass_plane, uint32_t n_passes, double* out, uint32_t* segments,
                                 hipStream_t stream);
+
+// include/tray_temporal.h section 2 (tray_temporal.hip).
+// One reprojection step over the out.width x out.height frame: p's scene and camera fields and
+// p.width, p.height. `history` and `prev` both null: the first frame. `record` nullable (zeroed
+// on `stream` ahead of the launch). use_bvh and bound as for launch_scene_hit.
+hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
+                                const tray_temporal_params& tp, const double* frame,
+                                const tray_temporal_state* history, const tray_temporal_state& out,
+                                tray_temporal_record* record, hipStream_t stream);
 
 }  // namespace tray

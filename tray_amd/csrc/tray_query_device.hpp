@@ -1,5 +1,6 @@
-// tray_query_device.hpp — the device side the ray-query kernels (tray_query.hip) and the
-// pixel-list renderer (tray_adaptive.hip) share: one ray's Scene.Hit and occlusion
+// tray_query_device.hpp — the device side the ray-query kernels (tray_query.hip), the
+// pixel-list renderer (tray_adaptive.hip) and the temporal step (tray_temporal.hip, which
+// uses query_hit and query_args) share: one ray's Scene.Hit and occlusion
 // (query_hit, query_occluded) over tray_device.hpp's traversal with the queries' stack
 // policy, one recursion level of RayColor on a plain path state (query_shade with its
 // scatter_step), and the host-side launch arguments that go with them (query_args).

@@ -334,6 +334,27 @@ def RichSceneCamera() -> Camera:  # ray/camera.go:144-154
                   cs.focus_distance, cs.aperture)
 
 
+def orbit_position(position: Vec3, look_at: Vec3, up: Vec3, degrees: float) -> Vec3:
+    """`position` turned about `look_at` around the axis `up` by `degrees` (Rodrigues' rotation; an
+    all-zero `up` means (0, 1, 0), as Camera.Initialize defaults it)."""
+    k = np.asarray(up, dtype=np.float64)
+    if not k.any():
+        k = np.array([0.0, 1.0, 0.0])
+    k = k / math.sqrt(float(k @ k))
+    v = np.asarray(position, dtype=np.float64) - np.asarray(look_at, dtype=np.float64)
+    c, s = math.cos(math.radians(degrees)), math.sin(math.radians(degrees))
+    r = v * c + np.cross(k, v) * s + k * (float(k @ v) * (1.0 - c))
+    return tuple((r + np.asarray(look_at, dtype=np.float64)).tolist())
+
+
+def Orbit(camera: Camera, degrees: float) -> Camera:
+    """A copy of `camera` turned about its LookAt around its Up axis by `degrees` (not initialized)."""
+    return Camera(orbit_position(camera.Position, camera.LookAt, camera.Up, degrees), tuple(camera.LookAt),
+                  tuple(camera.Up), camera.VerticalFoV, camera.FocalLength, camera.FocusDistance, camera.Aperture)
+
+
+ORBIT_STEP_DEGREES = 1.0  # the CLI's default -orbit-step (tools/temporal_sweep.py, DESIGN.md 8q)
+
 # --------------------------------------------------------------------- tracer
 _CAMERA_FIELDS = ("Position", "LookAt", "Up", "VerticalFoV", "FocalLength", "FocusDistance", "Aperture")
 
@@ -823,6 +844,87 @@ class Tracer:  # ray/tracer.go:25-36
         self.passes = int(self.counts.max())
         self.imageData[:] = rgba.cpu().numpy()
         return self.imageData
+
+    def RenderSequence(self, scene: Scene | None, cameras, denoise: bool = False, **overrides) -> list:
+        """A moving camera that keeps what it has seen (include/tray_temporal.h): frame k is rendered
+        through cameras[k] (a sequence of Camera objects, each initialized here for the tracer's size
+        as Render does) as progressive pass k of the tracer's one seed, so a still camera sees
+        independent samples, and tray_temporal_step_async reprojects the accumulated history of
+        frame k - 1 into it and folds the new frame in. The render, the step, with denoise=True the
+        guided filter (tray_denoise_async on the feature buffers of the current camera,
+        tray_render_aov_async) and the sRGB encoding are enqueued on one stream over two ping-pong
+        states; nothing is read back before the last frame is enqueued.
+
+        overrides: fields of tray_temporal_params (max_history, depth_tolerance, snap, flags).
+        Returns the list of (H, W, 4) uint8 RGBA frames and keeps the last in imageData; `linear`
+        holds the last accumulated FP64 frame (before the filter), `age` its (H, W) int32 ages, `fresh`
+        and `mean_age` the per-frame lists from the records (fresh pixels; the mean output age).
+        ValueError for an empty sequence, an entry that is not a Camera or an unknown override, before
+        any device work. No Go counterpart."""
+        cameras = list(cameras) if cameras is not None else []
+        if not cameras:
+            raise ValueError("cameras must hold at least one Camera")
+        if not all(isinstance(c, Camera) for c in cameras):
+            raise ValueError("cameras must be a sequence of Camera objects")
+        unknown = sorted(set(overrides) - {n for n, _ in _lib.TemporalParams._fields_})
+        if unknown or "reserved" in overrides:
+            raise ValueError(f"unknown temporal parameters {unknown or ['reserved']}")
+        tp = _lib.temporal_params(**overrides)
+        import torch
+
+        scene = self._apply_defaults(scene)
+        h, w = self.height, self.width
+        for c in cameras:
+            c.Initialize(w, h)
+        object.__setattr__(self, "Camera", cameras[-1])
+        device = int(self.Devices[0] if self.Devices else self.Device)
+        where = torch.device(f"cuda:{device}")
+        self.seed = self._seed()  # once: every frame is a pass of this stream
+        self.age = np.zeros((h, w), dtype=np.int32)
+        self.fresh, self.mean_age = [], []
+        if h * w == 0:
+            return [self.imageData.copy() for _ in cameras]
+        stream = torch.cuda.current_stream(where).cuda_stream
+        dev = scene._device_scene(device)
+        f64 = dict(dtype=torch.float64, device=where)
+
+        def planes():
+            t = dict(colour=torch.empty((h, w, 3), **f64), age=torch.empty((h, w), dtype=torch.int32, device=where),
+                     index=torch.empty((h, w), dtype=torch.int32, device=where), depth=torch.empty((h, w), **f64))
+            return t, _lib.TemporalState(t["colour"].data_ptr(), t["age"].data_ptr(), t["index"].data_ptr(),
+                                         t["depth"].data_ptr(), w, h)
+
+        states = [planes(), planes()]
+        frame = torch.empty((h, w, 3), **f64)
+        records = torch.empty((len(cameras), 2), dtype=torch.int64, device=where)
+        rgba = torch.empty((len(cameras), h, w, 4), dtype=torch.uint8, device=where)
+        aov = None
+        if denoise:
+            aov = {name: torch.empty((h, w, 3)[: 3 if ch > 1 else 2], **f64)
+                   for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1))}
+        for k, cam in enumerate(cameras):
+            params = _lib.make_params(w, h, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, self.seed, 0, h,
+                                      pass_=k)
+            dev.render_async(cam._state, params, frame.data_ptr(), None, stream)
+            out = states[k & 1]
+            _lib.temporal_step_async(dev.handle, cam._state, cameras[k - 1]._state if k else None, tp,
+                                     frame.data_ptr(), states[(k - 1) & 1][1] if k else None, out[1],
+                                     records[k].data_ptr(), stream)
+            shown = out[0]["colour"]
+            if denoise:
+                dev.render_aov_async(cam._state, params, aov["albedo"].data_ptr(), aov["normal"].data_ptr(),
+                                     aov["depth"].data_ptr(), stream=stream)
+                shown = self._denoise_device(torch, shown, aov, {})
+            _lib.linear_to_srgba_async(shown.data_ptr(), h * w, rgba[k].data_ptr(), device, stream)
+        last = states[(len(cameras) - 1) & 1][0]
+        self.linear[:] = last["colour"].cpu().numpy()
+        self.age = last["age"].cpu().numpy()
+        rec = records.cpu().numpy()
+        self.fresh = [int(r[0]) for r in rec]
+        self.mean_age = [float(r[1]) / (h * w) for r in rec]
+        frames = [f.copy() for f in rgba.cpu().numpy()]
+        self.imageData[:] = frames[-1]
+        return frames
 
     def RenderLines(self, idx: int, yStart: int, yEnd: int, scene: Scene) -> None:  # ray/tracer.go:120-155
         """Render rows [yStart, yEnd) with the current (initialized) camera and
