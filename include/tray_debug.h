@@ -42,6 +42,9 @@
  *                         this many paths finds their hits with the whole wave
  *                         scanning every sphere, one path at a time (0: never;
  *                         default 2) (same bits)
+ *   "plain_instance"      0: every launch takes the generic megakernel instance, also
+ *                         the launches that qualify for the plain-frame instance, whose
+ *                         launch options are compiled in (same bits)
  */
 #ifndef TRAY_DEBUG_H
 #define TRAY_DEBUG_H
@@ -61,6 +64,27 @@ int tray_debug_clear(const char *name);
  * host polls the same words while the launch runs). Writes min(*n_out, capacity) counters;
  * *n_out is the number of tile rows, 0 before any such render. */
 int tray_debug_progress_counts(int32_t device, uint64_t *counts, int32_t capacity, int32_t *n_out);
+
+/* What a launch is, for tray_debug_plain_instance: the buffers it has and the kernel family it runs. */
+#define TRAY_PLAIN_FACT_BVH 1u          /* the BVH kernel (not the linear scan) */
+#define TRAY_PLAIN_FACT_STATS 2u        /* tray_render_stats_async */
+#define TRAY_PLAIN_FACT_PROGRESS 4u     /* live progress */
+#define TRAY_PLAIN_FACT_STACK_SPILL 8u  /* the traversal stack overflows LDS */
+#define TRAY_PLAIN_FACT_SEGMENTS 16u    /* a segment-count buffer */
+#define TRAY_PLAIN_FACT_COUNTING 32u    /* a counting launch (the first of a work-order key) */
+#define TRAY_PLAIN_FACT_CANDIDATES 64u  /* primary-ray candidate records */
+#define TRAY_PLAIN_FACT_WORK_ORDER 128u /* a work order */
+/* The library's own choice between the generic megakernel instance (*plain_out = 0) and the
+ * plain-frame instance (1) for a launch with these properties: `facts` (bits above), rays per
+ * pixel, tile_rows of tray_params, the scene's out-of-tree spheres, tree nodes and spheres per leaf
+ * at most (tray_scene_info), on-chip sums
+ * `acc` (0 none, 1 one per 64-sample chunk, 2 one per pixel-pass), LDS layout `lds_mode` (0 / 1 /
+ * 2). Host only: no device is touched. The "plain_instance" knob applies. */
+int tray_debug_plain_instance(uint32_t facts, int32_t rays_per_pixel, int32_t tile_rows, int32_t n_global,
+                              int32_t n_nodes, int32_t leaf_max, int32_t acc, int32_t lds_mode,
+                              int32_t *plain_out);
+/* Launches (one per band) that took the plain-frame instance since the library was loaded. */
+int tray_debug_plain_launches(uint64_t *count_out);
 
 #ifdef __cplusplus
 }

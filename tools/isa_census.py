@@ -39,7 +39,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tray_amd", "csrc", "tray_kernel.hip")
-KERNEL = "_ZN4tray13render_kernelILi1ELb1ELb0ELb0ELb0ELi1ELi5ELb0EEEvNS_12KernelParamsE"  # --layout 2: ...ILi2E...
+KERNEL = "_ZN4tray13render_kernelILi1ELb1ELb0ELb0ELb0ELi1ELi5ELb0ENS_9LaunchAskEEEvNS_12KernelParamsE"  # --layout 2: ...ILi2E...
+# --instance plain: the plain-frame instance (launch options compiled in)
+INSTANCE = {"generic": "NS_9LaunchAskE", "plain": "NS_10PlainFrameE"}
 LLVM = "/opt/rocm/lib/llvm/bin"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-mllvm",
          "-amdgpu-atomic-optimizer-strategy=None"]
@@ -209,11 +211,13 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--markdown", action="store_true")
     ap.add_argument("--layout", type=int, default=1, help="LDS layout instance (1: book cover; 2: dense C5)")
+    ap.add_argument("--instance", default="generic", choices=sorted(INSTANCE),
+                    help="generic: every launch option asked at run time; plain: the plain-frame instance")
     ap.add_argument("--list", default=None, metavar="PHASE",
                     help="print the hot instructions of one phase (address, instruction, innermost function:line)")
     args = ap.parse_args()
     global KERNEL
-    KERNEL = KERNEL.replace("ILi1E", f"ILi{args.layout}E")
+    KERNEL = KERNEL.replace("ILi1E", f"ILi{args.layout}E").replace(INSTANCE["generic"], INSTANCE[args.instance])
 
     co = build(args.work)
     insts = disassemble(co)
@@ -252,6 +256,8 @@ def main():
             print(f"{i['addr']:6x}  {i['mn']:<24} {i['ops'][:48]:<48} {st[0][0][:40]}:{st[0][1]}")
         static[key]["inst"] += 1
         static[key]["unit:" + u] += 1
+        if i["mn"].startswith("s_cmp"):
+            static[key]["unit:scmp"] += 1  # scalar compares (also counted under salu)
         if u == "valu":
             static[key]["valu"] += 1
             static[key]["c:" + valu_class(i["mn"])] += 1
@@ -284,13 +290,16 @@ def main():
             if ph in ("node_ctl", "node"):
                 # the phase's static code is all the unrolled node steps (kSteps copies), and
                 # node_iters counts every step executed: one copy per count
-                n /= int(re.search(r"Li(\d+)ELb[01]EEEv", KERNEL).group(1))
+                n /= int(re.search(r"Li(\d+)ELb[01]ENS_", KERNEL).group(1))
             for k, v in static[ph].items():
                 if k == "valu" or k.startswith("c:"):
                     dyn[k] += v * n
                     dyn_group[GROUP[ph]][k] += v * n
+                if k.startswith("unit:"):  # every unit, for the scalar side: an upper bound (arms not taken count too)
+                    dyn[k] += v * n
         est = {"source": os.path.relpath(args.phase, ROOT), "weights": {ph: WEIGHT[ph] for ph in WEIGHT},
                "valu_per_frame": round(dyn["valu"]),
+               "units_per_frame": {k[5:]: round(v) for k, v in sorted(dyn.items()) if k.startswith("unit:")},
                "classes_per_frame": {k[2:]: round(v) for k, v in sorted(dyn.items()) if k.startswith("c:")},
                "by_group": {g: {"valu": round(c["valu"]), **{k[2:]: round(v) for k, v in sorted(c.items()) if k.startswith("c:")}}
                             for g, c in dyn_group.items()}}

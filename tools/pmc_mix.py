@@ -19,6 +19,8 @@ def main():
     ap.add_argument("--label", default="")
     ap.add_argument("--frames", type=int, default=16, help="frames per launch of the profiled bench command")
     ap.add_argument("--config", default="c2", help="bench config: picks the kernel instance (how r is summed)")
+    ap.add_argument("--instance", default="", help="only launches whose kernel name holds this, e.g. PlainFrame for the "
+                    "plain-frame instance or LaunchAsk for the generic one of the same shape (DESIGN.md 8r)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from bench import CONFIGS
@@ -34,7 +36,7 @@ def main():
             # the timed kernel: render_kernel<mode, true, false (no stats), spill>
             # the timed BVH kernel: render_kernel<layout, true, false (no stats), false (no spill), false, kAcc (on-chip sums), S (node steps)>
             # (layout 1 for the book cover, 2 for the dense C5 scene)
-            if "render_kernel<" not in name or want not in name:
+            if "render_kernel<" not in name or want not in name or a.instance not in name:
                 continue
             kernel = name
             key = (row["Counter_Name"], row["Dispatch_Id"])

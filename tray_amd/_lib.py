@@ -361,10 +361,14 @@ assert ctypes.sizeof(TemporalState) == 40 and ctypes.sizeof(TemporalParams) == 3
 assert ctypes.sizeof(TemporalRecord) == 16 and TEMPORAL_RECORD_DTYPE.itemsize == 16
 
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
-DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear", "tray_debug_progress_counts")
+DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear", "tray_debug_progress_counts", "tray_debug_plain_instance",
+                 "tray_debug_plain_launches")
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
                "primary_candidates", "resolve_staged", "wave_chunks", "scene_contexts", "grid_reserve",
-               "work_order", "coop_lanes")
+               "work_order", "coop_lanes", "plain_instance")
+# tray_debug_plain_instance's `facts` bits (TRAY_PLAIN_FACT_*).
+PLAIN_FACTS = {"bvh": 1, "stats": 2, "progress": 4, "stack_spill": 8, "segments": 16, "counting": 32,
+               "candidates": 64, "work_order": 128}
 
 # tray_progress_fn: void (*)(int32_t rows, void *user)
 PROGRESS_FN = ctypes.CFUNCTYPE(None, ctypes.c_int32, ctypes.c_void_p)
@@ -493,6 +497,9 @@ def lib(path: str | None = None) -> ctypes.CDLL:
     if hasattr(L, "tray_debug_progress_counts"):
         L.tray_debug_progress_counts.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
                                                  ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(L, "tray_debug_plain_instance"):  # absent from older builds (A/B tools)
+        L.tray_debug_plain_instance.argtypes = [ctypes.c_uint32] + [i32] * 7 + [ctypes.POINTER(i32)]
+        L.tray_debug_plain_launches.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     _libs[path] = L
     return L
 
@@ -537,6 +544,26 @@ def progress_counts(device: int = 0) -> np.ndarray:
         check(lib().tray_debug_progress_counts(device, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n.value,
                                                ctypes.byref(n)))
     return counts
+
+
+def plain_instance(facts, rays_per_pixel: int, tile_rows: int, n_global: int, n_nodes: int, leaf_max: int, acc: int,
+                   lds_mode: int) -> bool:
+    """tray_debug_plain_instance: whether a launch with these properties (`facts`: names of
+    PLAIN_FACTS) takes the megakernel's plain-frame instance. Host only."""
+    bits = 0
+    for name in facts:
+        bits |= PLAIN_FACTS[name]
+    out = ctypes.c_int32(-1)
+    check(lib().tray_debug_plain_instance(bits, rays_per_pixel, tile_rows, n_global, n_nodes, leaf_max, acc,
+                                          lds_mode, ctypes.byref(out)))
+    return out.value == 1
+
+
+def plain_launches() -> int:
+    """tray_debug_plain_launches: launches that took the plain-frame instance so far."""
+    n = ctypes.c_uint64(0)
+    check(lib().tray_debug_plain_launches(ctypes.byref(n)))
+    return int(n.value)
 
 
 def clear_debug_knobs(lib_path: str | None = None) -> None:

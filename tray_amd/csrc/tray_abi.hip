@@ -42,7 +42,7 @@ static std::atomic<long long> g_knob_value[kKnobCount];
 static std::atomic<bool> g_knob_set[kKnobCount];
 static const char* const kKnobNames[kKnobCount] = {
     "acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep", "primary_candidates",
-    "resolve_staged", "wave_chunks", "scene_contexts", "grid_reserve", "work_order", "coop_lanes"};
+    "resolve_staged", "wave_chunks", "scene_contexts", "grid_reserve", "work_order", "coop_lanes", "plain_instance"};
 
 bool debug_knob(DebugKnob k, long long* v) {
     if (!g_knob_set[k].load(std::memory_order_acquire)) return false;
@@ -328,6 +328,37 @@ int tray_debug_progress_counts(int32_t device, uint64_t* counts, int32_t capacit
     const Slot& sl = st->slot(0);  // tray_render_progress renders through slot 0; it has returned, so the stream is idle
     *n_out = sl.prog_host ? sl.prog_tile_rows : 0;
     for (int32_t t = 0; t < *n_out && t < capacity; ++t) counts[t] = (uint64_t)sl.prog_host[t];
+    return TRAY_OK;
+}
+
+int tray_debug_plain_instance(uint32_t facts, int32_t rays_per_pixel, int32_t tile_rows, int32_t n_global,
+                              int32_t n_nodes, int32_t leaf_max, int32_t acc, int32_t lds_mode, int32_t* plain_out) {
+    if (!plain_out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null argument");
+    // Host-filled parameters: the predicate reads the pointers only as set or null.
+    static unsigned long long word[4];
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    k.stats = facts & TRAY_PLAIN_FACT_STATS ? word : nullptr;
+    k.progress = facts & TRAY_PLAIN_FACT_PROGRESS ? word : nullptr;
+    k.segments = facts & TRAY_PLAIN_FACT_SEGMENTS ? reinterpret_cast<uint32_t*>(word) : nullptr;
+    k.tile_cost = facts & TRAY_PLAIN_FACT_COUNTING ? reinterpret_cast<uint32_t*>(word) : nullptr;
+    k.cand = facts & TRAY_PLAIN_FACT_CANDIDATES ? reinterpret_cast<const uint4*>(word) : nullptr;
+    k.tile_order = facts & TRAY_PLAIN_FACT_WORK_ORDER ? reinterpret_cast<const uint32_t*>(word) : nullptr;
+    k.spp = rays_per_pixel;
+    k.tile_rows = tile_rows;
+    k.n_global = n_global;
+    k.n_nodes = n_nodes;
+    k.leaf_single = leaf_max == 1 ? 1 : 0;  // as prepare_render fills it
+    *plain_out = plain_frame_launch(k, (facts & TRAY_PLAIN_FACT_BVH) != 0, (facts & TRAY_PLAIN_FACT_STACK_SPILL) != 0,
+                                    acc, lds_mode)
+                     ? 1
+                     : 0;
+    return TRAY_OK;
+}
+
+int tray_debug_plain_launches(uint64_t* count_out) {
+    if (!count_out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null argument");
+    *count_out = plain_launch_count();
     return TRAY_OK;
 }
 

@@ -144,6 +144,31 @@ __device__ __forceinline__ const KernelParams& kp_fresh() {
     return *(const KernelParams*)q;
 }
 
+// Launch options compiled in (render_kernel's kOpt). The render loop asks questions
+// whose answers are fixed for a whole launch (is there a segment buffer, is this a counting launch,
+// are the rows contiguous, ...), at every use, through kp_fresh(): a scalar load, a wait, a compare
+// and a branch each time. An option set answers some of them at compile time: a `true` below means
+// "the launch was checked to have this property" (plain_frame_launch, tray_kernel.hip), the test
+// and its dead arm are not compiled, and `false` means "ask at run time", the code as it always was.
+// LaunchAsk asks everything and is the default everywhere, so code that names no option set is
+// textually and in its instructions what it was.
+struct LaunchAsk {
+    static constexpr bool kNoSegments = false;   // KernelParams::segments is null
+    static constexpr bool kNoCount = false;      // KernelParams::tile_cost is null (no counting launch)
+    static constexpr bool kCand = false;         // KernelParams::cand is set (primary-ray candidates)
+    static constexpr bool kMultiSample = false;  // rays per pixel > 1 (the anti-aliasing disc is drawn)
+    static constexpr bool kContigRows = false;   // KernelParams::tile_rows <= 0 (no row tiles)
+    static constexpr bool kOrdered = false;      // KernelParams::tile_order is set (a work order)
+    static constexpr bool kOneGlobal = false;    // exactly one sphere outside the tree
+    static constexpr bool kHasNodes = false;     // the tree has a root
+    static constexpr bool kSingleLeaf = false;   // SceneView::single: one sphere per leaf
+};
+// The plain frame: every option fixed.
+struct PlainFrame {
+    static constexpr bool kNoSegments = true, kNoCount = true, kCand = true, kMultiSample = true, kContigRows = true,
+                          kOrdered = true, kOneGlobal = true, kHasNodes = true, kSingleLeaf = true;
+};
+
 // The draw block of (pixel, sample, bounce, purpose) (include/tray.h, rng.hpp draw_block).
 __device__ __forceinline__ Block draw(const KernelParams& p, uint32_t pixel, uint32_t sample, uint32_t bounce,
                                      uint32_t purpose) {
@@ -168,11 +193,16 @@ __device__ __forceinline__ Block camera_block(const KernelParams& p, uint32_t pi
 // Camera.GetRay (ray/camera.go:113-142). The sample's camera block `u` feeds the
 // anti-aliasing disc (words 0,1; ray/tracer.go:136-139, only when r > 1) and the
 // lens disc (words 2,3, only when the aperture is open).
+template <class Opt = LaunchAsk>
 __device__ __forceinline__ void get_ray(const KernelParams& p, const Block& u, double px, double py, D3& origin,
                                         D3& dir) {
     double ox = 0.0, oy = 0.0;
     const double aperture = p.cam.aperture;
-    if (p.spp > 1) disc(u.x0, u.x1, p.ray_radius, ox, oy);
+    if constexpr (Opt::kMultiSample) {
+        disc(u.x0, u.x1, p.ray_radius, ox, oy);
+    } else {
+        if (p.spp > 1) disc(u.x0, u.x1, p.ray_radius, ox, oy);
+    }
     const D3 pos = ld3(p.cam.position);
     const D3 p00 = ld3(p.cam.pixel00);
     const D3 pxv = ld3(p.cam.pixel_x);
@@ -201,7 +231,9 @@ __device__ __forceinline__ uint32_t udiv(uint32_t n, const FastDiv& f, uint32_t&
 }
 
 // Compact output row j -> image row y (see tray_params in include/tray.h).
+template <class Opt = LaunchAsk>
 __device__ __forceinline__ int32_t row_of(const KernelParams& p, int32_t j) {
+    if constexpr (Opt::kContigRows) return p.y_start + j;
     if (p.tile_rows <= 0) return p.y_start + j;
     uint32_t within;
     const int32_t t = (int32_t)udiv((uint32_t)j, p.div_tile_rows, within);
@@ -431,14 +463,19 @@ __device__ __forceinline__ void test_slot(Trav& T, const SceneView& sv, int32_t 
 // Scene.Hit's FP64 setup for a new segment: a = |dir|^2 and its reciprocal,
 // no hit yet, and the spheres kept out of the tree (tray_bvh.cpp, at most
 // kBvhGlobals) tested first; a hit seeds the culling distance of the traversal.
+template <class Opt = LaunchAsk>
 __device__ __forceinline__ void trav_globals(Trav& T, const SceneView& sv, const D3& org, const D3& dir) {
     T.a = length_sq(dir);  // hoisted: same bits as per sphere
     T.a_inv = rcp_cr(T.a);
     T.closest = __builtin_inf();
     T.slot = -1;
+    if constexpr (Opt::kOneGlobal) {
+        test_slot(T, sv, sv.global_first, org, dir);
+    } else {
 #pragma unroll
-    for (int32_t g = 0; g < kBvhGlobals; ++g)
-        if (g < sv.n_global) test_slot(T, sv, sv.global_first + g, org, dir);
+        for (int32_t g = 0; g < kBvhGlobals; ++g)
+            if (g < sv.n_global) test_slot(T, sv, sv.global_first + g, org, dir);
+    }
 }
 
 // The direction lengths the FP32 slab test is conservative for (tray_bvh.cpp, "Range of
@@ -452,8 +489,9 @@ __device__ __forceinline__ void trav_globals(Trav& T, const SceneView& sv, const
 __device__ __forceinline__ bool slab_dir_ok(double a) { return a >= 1e-30 && a <= 1e30; }
 
 // The FP32 traversal setup of a segment whose FP64 part (trav_globals) is done.
+template <class Opt = LaunchAsk>
 __device__ __forceinline__ void trav_begin32(Trav& T, const SceneView& sv, const D3& org, const D3& dir) {
-    T.cur = sv.n_nodes > 0 ? 0u : kBvhNone;  // the root
+    T.cur = Opt::kHasNodes || sv.n_nodes > 0 ? 0u : kBvhNone;  // the root
     T.sp = 0;
     T.top = ~0u;
     float dxf = (float)dir.x, dyf = (float)dir.y, dzf = (float)dir.z;
@@ -475,10 +513,11 @@ __device__ __forceinline__ void trav_begin32(Trav& T, const SceneView& sv, const
     T.tlim = f32_up(T.closest);
 }
 
+template <class Opt = LaunchAsk>
 __device__ __forceinline__ void trav_begin(Trav& T, const SceneView& sv, const D3& org, const D3& dir) {
     T.tlim = __builtin_inff();
-    trav_globals(T, sv, org, dir);
-    trav_begin32(T, sv, org, dir);
+    trav_globals<Opt>(T, sv, org, dir);
+    trav_begin32<Opt>(T, sv, org, dir);
 }
 
 // Push `key` if valid. The store is unconditional: with no push it writes
@@ -611,11 +650,11 @@ __device__ __forceinline__ void leaf_spheres(Trav& T, const SceneView& sv, uint3
 }
 
 // Test the spheres of leaf T.cur (FP64, any-order rule), then pop the next entry.
-template <class Stk>
+template <class Opt = LaunchAsk, class Stk>
 __device__ __forceinline__ void trav_leaf(Trav& T, const SceneView& sv, const Stk& S, const D3& org,
                                               const D3& dir, uint32_t& tested) {
     const uint32_t below = stack_load(S, max(T.sp - 1, 0));  // read ahead for the pop
-    if (sv.single) {  // one sphere per leaf: the leaf index is its slot (no leaf table, no loop)
+    if (Opt::kSingleLeaf || sv.single) {  // one sphere per leaf: the leaf index is its slot (no leaf table, no loop)
         test_slot(T, sv, (int32_t)(T.cur & (kBvhLeafBit - 1u)), org, dir);
         tested = 1;
     } else {

@@ -37,6 +37,7 @@ enum DebugKnob {
     kKnobGridReserve,
     kKnobWorkOrder,
     kKnobCoopLanes,
+    kKnobPlainInstance,
     kKnobCount
 };
 // True, with the value in *v, when the knob is set.

@@ -37,6 +37,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 
 #include "tray_diag.hpp"  // the diagnostic builds' hooks; it includes tray_device.hpp
 
@@ -239,13 +240,15 @@ __device__ __forceinline__ uint32_t take_chunk(const KernelParams& p, UniPtr uni
 // tile_order[t], looked up once per chunk by the caller (`tile`, chunk_tile);
 // without an order, tile t. A chunk never straddles two tiles (a tile is 64
 // pixels x r x passes items, a multiple of 64).
+template <class Opt = LaunchAsk>
 __device__ __forceinline__ bool decode_item(const KernelParams& p, uint32_t i, uint32_t tile, int32_t& x, int32_t& j,
                                             uint32_t& s, uint32_t& k) {
     k = 0;
     uint32_t q = udiv(i, p.div_spp, s);
     if (p.passes > 1) q = udiv(q, p.div_passes, k);
     const uint32_t r = q & 63u;
-    if (!p.tile_order) tile = q >> 6;
+    if constexpr (!Opt::kOrdered)
+        if (!p.tile_order) tile = q >> 6;
     uint32_t tx;
     const uint32_t ty = udiv(tile, p.div_tiles_x, tx);
     x = (int32_t)(tx * 8u + (r & 7u));
@@ -254,16 +257,19 @@ __device__ __forceinline__ bool decode_item(const KernelParams& p, uint32_t i, u
     return x < p.width && jb < p.band_rows;
 }
 // The band tile chunk c renders (wave-uniform: one scalar load per chunk taken).
+template <class Opt = LaunchAsk>
 __device__ __forceinline__ uint32_t chunk_tile(const KernelParams& p, uint32_t c) {
-    if (!p.tile_order) return 0u;  // unused: decode_item takes q >> 6
+    if constexpr (!Opt::kOrdered)
+        if (!p.tile_order) return 0u;  // unused: decode_item takes q >> 6
     uint32_t rem;
     return __builtin_amdgcn_readfirstlane(p.tile_order[udiv(c, p.div_chunks_per_tile, rem)]);
 }
 
 // Start sample s of pixel (x, compact row j) in the lane: its camera ray.
+template <class Opt = LaunchAsk>
 __device__ __forceinline__ void start_sample(const KernelParams& p, Lane& L, uint32_t item, int32_t x,
                                              int32_t j, uint32_t s) {
-    const int32_t y = row_of(p, j);
+    const int32_t y = row_of<Opt>(p, j);
     L.item = item;
     L.x = x;
     L.j = j;
@@ -273,7 +279,7 @@ __device__ __forceinline__ void start_sample(const KernelParams& p, Lane& L, uin
     L.segments = 0;
     L.thr = d3(1, 1, 1);
     L.busy = true;
-    get_ray(p, camera_block(p, L.pixel, s), (double)x, (double)y, L.org, L.dir);
+    get_ray<Opt>(p, camera_block(p, L.pixel, s), (double)x, (double)y, L.org, L.dir);
 }
 
 // A path ended with `color`: store it in the band's sample buffer (the resolve
@@ -283,7 +289,7 @@ __device__ __forceinline__ void start_sample(const KernelParams& p, Lane& L, uin
 // the colour is already scaled by 2^acc_shift (through the background) and is
 // rounded to an integer (tray_kernel.hpp), added with a non-returning LDS
 // atomic (exact, so in any order).
-template <bool kStats, int kAcc>
+template <bool kStats, int kAcc, class Opt = LaunchAsk>
 __device__ __forceinline__ void end_path(const KernelParams& p, Lane& L, const D3& color, Stats& st,
                                          const AccCtx& acc) {
     if constexpr (kAcc) {
@@ -303,9 +309,10 @@ __device__ __forceinline__ void end_path(const KernelParams& p, Lane& L, const D
         if (p.tile_cost)
             __hip_atomic_fetch_add(acc.counts + L.slot, L.segments, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 #else
-        if (p.tile_cost)
-            __hip_atomic_fetch_add(acc.counts + L.slot, L.segments * L.segments, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_WAVEFRONT);
+        if constexpr (!Opt::kNoCount)
+            if (p.tile_cost)
+                __hip_atomic_fetch_add(acc.counts + L.slot, L.segments * L.segments, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WAVEFRONT);
 #endif
     } else {
         double* o = p.samples + (size_t)L.item * 3;
@@ -313,7 +320,8 @@ __device__ __forceinline__ void end_path(const KernelParams& p, Lane& L, const D
         o[1] = color.y;
         o[2] = color.z;
     }
-    if (p.segments) atomicAdd(p.segments + (size_t)L.j * (size_t)p.width + (size_t)L.x, L.segments);
+    if constexpr (!Opt::kNoSegments)
+        if (p.segments) atomicAdd(p.segments + (size_t)L.j * (size_t)p.width + (size_t)L.x, L.segments);
     if constexpr (kStats) st.segments += L.segments;
     L.busy = false;
 }
@@ -393,7 +401,7 @@ __device__ __forceinline__ uint64_t acc_all_slots(const KernelParams& p) {
 // Called only when the wave finds no free slot, and at exit: the busy lanes'
 // slots are found by one ballot per open slot. A wave's LDS operations complete
 // in issue order, so the reads see every addition its lanes made.
-template <int kAcc>
+template <int kAcc, class Opt = LaunchAsk>
 __device__ __forceinline__ uint64_t acc_retire(const KernelParams& p, const AccCtx& acc, uint64_t open, bool busy,
                                                uint32_t slot, uint32_t chunk_of, uint32_t lane) {
     uint64_t freed = 0;
@@ -411,10 +419,12 @@ __device__ __forceinline__ uint64_t acc_retire(const KernelParams& p, const AccC
         const uint32_t groups = 64u >> acc_rshift<kAcc>(p);
         // the chunk's Scene.Hit calls (a counting launch; 0 otherwise) ride in group 0's pad
         uint32_t count = 0u;
-        if (p.tile_cost) {
-            volatile LdsU32* n = acc.counts;  // after every add of the wave's lanes (LDS issue order)
-            count = n[lane];
-            n[lane] = 0u;
+        if constexpr (!Opt::kNoCount) {
+            if (p.tile_cost) {
+                volatile LdsU32* n = acc.counts;  // after every add of the wave's lanes (LDS issue order)
+                count = n[lane];
+                n[lane] = 0u;
+            }
         }
         for (uint32_t g = 0; g < groups; ++g) {
             const uint32_t slab = kAcc == 1 ? lane : lane * groups + g;
@@ -477,12 +487,12 @@ __device__ __forceinline__ bool shade_end_color(const KernelParams& p, const Lan
     return false;
 }
 // Returns false when the path ended here (stored; the lane is free).
-template <bool kStats, int kAcc, bool kWild>
+template <bool kStats, int kAcc, bool kWild, class Opt = LaunchAsk>
 __device__ __forceinline__ bool shade_end(const KernelParams& p, Lane& L, bool hit, double dir_lsq, Stats& st,
                                           const AccCtx& acc) {
     D3 color;
     if (shade_end_color<kWild>(p, L, hit, dir_lsq, color)) return true;
-    end_path<kStats, kAcc>(p, L, color, st, acc);
+    end_path<kStats, kAcc, Opt>(p, L, color, st, acc);
     return false;
 }
 
@@ -558,12 +568,12 @@ __device__ __forceinline__ bool shade_scatter_color(const KernelParams& p, Lane&
     return !ends;
 }
 // Returns false when the path ended here (absorbed: stored; the lane is free).
-template <bool kStats, int kAcc, bool kWild, typename GeoAt, typename MatAt>
+template <bool kStats, int kAcc, bool kWild, class Opt = LaunchAsk, typename GeoAt, typename MatAt>
 __device__ __forceinline__ bool shade_scatter(const KernelParams& p, Lane& L, double closest, double dir_lsq,
                                               GeoAt geo_at, MatAt mat_at, Stats& st, const AccCtx& acc) {
     D3 color;
     if (shade_scatter_color<kWild>(p, L, closest, dir_lsq, geo_at, mat_at, color)) return true;
-    end_path<kStats, kAcc>(p, L, color, st, acc);
+    end_path<kStats, kAcc, Opt>(p, L, color, st, acc);
     return false;
 }
 
@@ -663,8 +673,9 @@ __host__ __device__ constexpr size_t bvh_stack_bytes(int32_t slots) { return (si
 // kSteps: node steps per loop iteration at most (kDeepSteps for deep trees, launch_render).
 // kWild: the instance for scenes with an infinite or NaN albedo (shade_step), linear scan only:
 // such a scene renders through the reference's own loop, and no other instance carries its code.
+// kOpt: the launch's options compiled in (tray_device.hpp; LaunchAsk: every one asked at run time).
 template <int kLDS, bool kBVH, bool kStats, bool kSpill, bool kProg, int kAcc, int kSteps = TRAY_NODE_STEPS_MAX,
-          bool kWild = false>
+          bool kWild = false, class kOpt = LaunchAsk>
 __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_SIMD : TRAY_WAVES_PER_SIMD) void render_kernel(KernelParams p) {
     static_assert(!(kWild && (kBVH || kAcc != 0)), "kWild: linear scan, FP64 sums");
     extern __shared__ __attribute__((aligned(16))) double4 smem_all[];
@@ -843,8 +854,8 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                         // this refill have not started yet: their chunk is open regardless).
                         // (kChunkPixel: a lane given an item of a padding chunk holds no slot.)
                         const bool held = L.busy || (kChunkPixel ? fresh_real : fresh);
-                        acc_free = acc_retire<kAcc>(kp_fresh(), acc, acc_all_slots(kp_fresh()), held, L.slot, acc_chunk,
-                                                    lane);
+                        acc_free = acc_retire<kAcc, kOpt>(kp_fresh(), acc, acc_all_slots(kp_fresh()), held, L.slot,
+                                                          acc_chunk, lane);
                     }
                     if (acc_free == 0ull) {
                         // unreachable with nothing in flight: no chunk would hold a slot
@@ -885,7 +896,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                         pool_xs = -1;
                         run_first = kNoRun;
                         if (pool_next < pc.items) {
-                            if (decode_item(pc, pool_next, chunk_tile(pc, c), cx, pool_j, cs, cp)) {
+                            if (decode_item<kOpt>(pc, pool_next, chunk_tile<kOpt>(pc, c), cx, pool_j, cs, cp)) {
                                 pool_sample = (pc.pass0 + cp) * (uint32_t)pc.spp + cs - pool_next;
                                 pool_xs = cx;
                             }
@@ -899,7 +910,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                         pool_xs = (pool_xs & (int32_t)((1u << kXsShift) - 1u)) | (int32_t)(slot << kXsShift);
                     }
                 } else {
-                    pool_tile = chunk_tile(pc, c);
+                    pool_tile = chunk_tile<kOpt>(pc, c);
                     if constexpr (kAcc) {
                         // With 64 | r every item of a chunk is one pixel's: valid or padding
                         // together. A chunk of several pixel-passes (r | 64) may mix the two
@@ -907,7 +918,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                         int32_t cx, cj;
                         uint32_t cs, cp;
                         if (acc_rshift<kAcc>(p) < 6u ||
-                            (pool_next < pc.items && decode_item(pc, pool_next, pool_tile, cx, cj, cs, cp))) {
+                            (pool_next < pc.items && decode_item<kOpt>(pc, pool_next, pool_tile, cx, cj, cs, cp))) {
                             pool_slot = (uint32_t)__builtin_ctzll(acc_free);
                             acc_free &= ~(1ull << pool_slot);
                             acc_chunk = lane == pool_slot ? c : acc_chunk;
@@ -968,21 +979,26 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             uint32_t smp = 0, pass = 0;
             bool valid = fresh_real;  // kChunkPixel: the chunk's decode
             if constexpr (!kChunkPixel)
-                valid = L.item < pr.items && decode_item(pr, L.item, (uint32_t)L.x, x, j, smp, pass);
+                valid = L.item < pr.items && decode_item<kOpt>(pr, L.item, (uint32_t)L.x, x, j, smp, pass);
             if (valid) {
                 if constexpr (kProbed<kProbeRefill>) probe<kProbeRefill>();
                 // The pixel's primary-ray candidates, loaded before the camera ray is built.
                 uint4 cand = make_uint4(0u, 0u, 0u, kCandOverflow << 16);
-                if constexpr (kBVH)
-                    if (pr.cand) cand = pr.cand[(size_t)j * (size_t)pr.width + (size_t)x];
-                start_sample(pr, L, L.item, x, j,
+                if constexpr (kBVH) {
+                    if constexpr (kOpt::kCand) {
+                        cand = pr.cand[(size_t)j * (size_t)pr.width + (size_t)x];
+                    } else {
+                        if (pr.cand) cand = pr.cand[(size_t)j * (size_t)pr.width + (size_t)x];
+                    }
+                }
+                start_sample<kOpt>(pr, L, L.item, x, j,
                              kChunkPixel ? L.sample + L.item : (pr.pass0 + pass) * (uint32_t)pr.spp + smp);
                 if constexpr (Diag::kCameraRayBuilt<kStats>) dg.camera_ray_built();
                 if constexpr (kBVH) {
                     TRAY_MARK("refill_cand")
                     ++L.segments;
                     T.tlim = __builtin_inff();
-                    trav_globals(T, sv, L.org, L.dir);
+                    trav_globals<kOpt>(T, sv, L.org, L.dir);
                     if constexpr (kStats) st.spheres += (uint64_t)sv.n_global;
                     const uint32_t n_cand = cand.w >> 16;
                     // A camera ray's direction has whatever length Go's camera gives it
@@ -1006,7 +1022,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                         T.cur = kBvhNone;  // traversal done: the lane waits for the shade phase
                         cam_hit = true;
                     } else {
-                        trav_begin32(T, sv, L.org, L.dir);
+                        trav_begin32<kOpt>(T, sv, L.org, L.dir);
                     }
                 }
                 if constexpr (Diag::kCameraHitDone) dg.camera_hit_done();
@@ -1023,7 +1039,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 TRAY_MARK("refill_shade")
                 bool ended = false;
                 if (cam_hit) {
-                    if (shade_end<kStats, kAcc, false>(kp_fresh(), L, T.slot >= 0, T.a, st, acc))
+                    if (shade_end<kStats, kAcc, false, kOpt>(kp_fresh(), L, T.slot >= 0, T.a, st, acc))
                         T.cur = kTravHitCam;
                     else
                         ended = true;
@@ -1075,8 +1091,8 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 bool ended = false;
                 if (is_marked(T.cur)) {
                     TRAY_MARK("scatter")
-                    if (shade_scatter<kStats, kAcc, false>(kp_fresh(), L, T.closest, T.a, [&] { return sv.bgeo[T.slot]; },
-                                                           [&] { return sv.bmat[T.slot]; }, st, acc)) {
+                    if (shade_scatter<kStats, kAcc, false, kOpt>(kp_fresh(), L, T.closest, T.a, [&] { return sv.bgeo[T.slot]; },
+                                                                 [&] { return sv.bmat[T.slot]; }, st, acc)) {
                         ++L.segments;
                         if constexpr (Diag::kScatterSegment<kStats>)
                             dg.scatter_segment<kStats>(T.slot >= sv.global_first, L.dir, st);
@@ -1098,7 +1114,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                 if constexpr (Diag::kBeginPart) dg.begin_part(lane, T.cur);
                 if (T.cur == kTravReady) {
                     TRAY_MARK("begin")
-                    trav_begin(T, sv, L.org, L.dir);
+                    trav_begin<kOpt>(T, sv, L.org, L.dir);
                     if constexpr (kStats) st.spheres += (uint64_t)sv.n_global;
                 }
                 if constexpr (Diag::kPhase<kStats>) dg.phase_end<kProfBegin, kStats>(lane);
@@ -1158,7 +1174,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                     TRAY_MARK("leaf")
                     uint32_t tested;
                     if constexpr (kProbed<kProbeLeaf>) probe<kProbeLeaf>();
-                    trav_leaf(T, sv, S, L.org, L.dir, tested);
+                    trav_leaf<kOpt>(T, sv, S, L.org, L.dir, tested);
                     if constexpr (kStats) st.spheres += tested;
                     if constexpr (Diag::kLeafVisit<kStats>) dg.leaf_visit<kStats>(st, L.bounce);
                 }
@@ -1180,7 +1196,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
                     if constexpr (kProbed<kProbeShade64>) probe<kProbeShade64>();
                     // The end half (sky, last level); a hit that scatters is marked for the
                     // scatter step of the next iteration.
-                    if (shade_end<kStats, kAcc, false>(kp_fresh(), L, T.slot >= 0, T.a, st, acc))
+                    if (shade_end<kStats, kAcc, false, kOpt>(kp_fresh(), L, T.slot >= 0, T.a, st, acc))
                         T.cur = kTravHit;
                     else
                         ended = true;  // idle: T.cur stays kBvhNone, L.busy is false
@@ -1194,7 +1210,7 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
     }
     if constexpr (kProg) flush_progress(kp_fresh(), prog_cur, prog_cnt, lane);
     if constexpr (kAcc)  // every lane is idle
-        (void)acc_retire<kAcc>(kp_fresh(), acc, acc_all_slots(kp_fresh()) & ~acc_free, false, 0u, acc_chunk, lane);
+        (void)acc_retire<kAcc, kOpt>(kp_fresh(), acc, acc_all_slots(kp_fresh()) & ~acc_free, false, 0u, acc_chunk, lane);
     if constexpr (kStats) {
         // One atomic per wave: 3 per lane on three addresses serialised ~9 ms of tail
         // onto every instrumented launch (786 K device-scope atomics at C2).
@@ -1604,6 +1620,33 @@ static KernelFn pick_kernel(int lds_mode, bool bvh, bool stats, bool progress, b
                     : pick_kernel2<true, false, 0>(lds_mode, stats, progress, deep);
 }
 
+// The plain-frame instance: render_kernel with the launch's options compiled in
+// (PlainFrame, tray_device.hpp), for the launch the product runs frame after frame. True only when
+// every option PlainFrame fixes holds for this launch; everything else - stats, live progress, a
+// spilling stack, the linear scan, r = 16 / 32 (acc 2) or no on-chip sums (acc 0), a scene in global
+// memory, segment counts, a counting launch (the first of a work-order key), no work order (several
+// bands, the knob), no candidates, r = 1, row tiles, no or two out-of-tree spheres, an empty tree,
+// leaves of several spheres - takes the generic instance as before, and so does any launch while the
+// "plain_instance" knob is 0.
+// p.tile_order and p.tile_cost are the launch's (launch_render derives each band's from them).
+bool plain_frame_launch(const KernelParams& p, bool use_bvh, bool spill, int acc, int lds_mode) {
+    long long knob = 1;
+    if (debug_knob(kKnobPlainInstance, &knob) && knob == 0) return false;
+    return use_bvh && !spill && acc == 1 && (lds_mode == 1 || lds_mode == 2) && !p.stats && !p.progress &&
+           !p.segments && !p.tile_cost && p.cand && p.spp > 1 && p.tile_rows <= 0 && p.tile_order &&
+           p.n_global == 1 && p.n_nodes > 0 && p.leaf_single != 0;
+}
+static KernelFn pick_plain(int lds_mode, bool deep) {
+    if (lds_mode == 1)
+        return deep ? render_kernel<1, true, false, false, false, 1, kDeepSteps, false, PlainFrame>
+                    : render_kernel<1, true, false, false, false, 1, TRAY_NODE_STEPS_MAX, false, PlainFrame>;
+    return deep ? render_kernel<2, true, false, false, false, 1, kDeepSteps, false, PlainFrame>
+                : render_kernel<2, true, false, false, false, 1, TRAY_NODE_STEPS_MAX, false, PlainFrame>;
+}
+// Bands launched through the plain-frame instance since the library was loaded (tray_debug_plain_launches).
+static std::atomic<uint64_t> g_plain_launches{0};
+uint64_t plain_launch_count() { return g_plain_launches.load(std::memory_order_relaxed); }
+
 template <int kMode>
 static KernelFn pick_resolve2(int fmt) {
     if (fmt == kOutRGBF64) return resolve_kernel<kOutRGBF64, kMode>;
@@ -1811,9 +1854,12 @@ hipError_t launch_render(KernelParams p, bool use_bvh, const LaunchPlan& plan, h
     long long knob = 0;
     if (debug_knob(kKnobNodeDeep, &knob))  // A/B: force the instance
         deep = use_bvh && knob != 0;
-    const KernelFn fn = pick_kernel(lds_mode, use_bvh, stats, p.progress != nullptr,
-                                    use_bvh && p.stack_cap > p.stack_lds,
-                                    p.acc_slots <= 0 ? 0 : p.acc_rshift < 6u ? 2 : 1, deep, p.wild_att != 0);
+    const bool spill = use_bvh && p.stack_cap > p.stack_lds;
+    const int acc = p.acc_slots <= 0 ? 0 : p.acc_rshift < 6u ? 2 : 1;
+    const bool plain = plain_frame_launch(p, use_bvh, spill, acc, lds_mode);
+    const KernelFn fn = plain ? pick_plain(lds_mode, deep)
+                              : pick_kernel(lds_mode, use_bvh, stats, p.progress != nullptr, spill, acc, deep,
+                                            p.wild_att != 0);
     const KernelFn resolve = pick_resolve(p);
     // Per-device, per-(kernel, LDS size) launch setup, cached.
     struct Setup {
@@ -1888,6 +1934,7 @@ hipError_t launch_render(KernelParams p, bool use_bvh, const LaunchPlan& plan, h
         hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, stream, p);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
+        if (plain) g_plain_launches.fetch_add(1, std::memory_order_relaxed);
         hipLaunchKernelGGL(resolve, dim3((pixels + 255u) / 256u, p.passes), dim3(256), 0, stream, p);
         e = hipGetLastError();
         if (e != hipSuccess) {

@@ -168,6 +168,14 @@ struct LaunchPlan;
 hipError_t launch_render(KernelParams p, bool use_bvh, const LaunchPlan& plan, hipStream_t stream,
                          size_t samples_bytes, uint32_t* order_out = nullptr);
 
+// True when launch_render sends a launch with these filled parameters through the plain-frame
+// instance of the megakernel (its options compiled in; tray_kernel.hip). `spill`:
+// the traversal stack overflows LDS; `acc`: 0 no on-chip sums, 1 one per chunk, 2 per pixel-pass;
+// `lds_mode`: LaunchLayout::lds_mode. Host only: it reads p and the "plain_instance" knob.
+bool plain_frame_launch(const KernelParams& p, bool use_bvh, bool spill, int acc, int lds_mode);
+// Bands launched through the plain-frame instance since the library was loaded.
+uint64_t plain_launch_count();
+
 // Fixed-point accumulation. A sample's colour c (already scaled by 2^k through
 // the background) is rounded to the integer v = rint(c), |v| <= 2^kAccBits; any
 // sum of at most 64 such integers is itself an integer of magnitude <= 2^53, so
