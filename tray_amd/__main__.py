@@ -12,6 +12,9 @@ have no meaning here).
                                           # that have not converged yet (include/tray_adaptive.h)
     python -m tray_amd -r 4 -orbit 8 [-orbit-step DEG] [-denoise] ...  # a camera orbit that reuses each
                                           # last frame by temporal reprojection (include/tray_temporal.h)
+    python -m tray_amd -r 4 -orbit 8 -variance [-refill [R]] [-denoise] ...  # the same, carrying M2: R more passes
+                                          # for the fresh pixels of each frame, and the variance-guided filter
+                                          # (include/tray_temporal_variance.h)
 """
 from __future__ import annotations
 
@@ -69,6 +72,13 @@ def main(argv=None) -> int:
                          "and the mean age per frame and saves the last frame; -denoise applies")
     ap.add_argument("-orbit-step", type=float, default=ray.ORBIT_STEP_DEGREES, metavar="DEG", dest="orbit_step",
                     help="with -orbit: degrees between frames")
+    ap.add_argument("-variance", action="store_true",
+                    help="with -orbit: carry M2 with the colour (include/tray_temporal_variance.h); -denoise is then "
+                         "the variance-guided filter")
+    ap.add_argument("-refill", type=int, nargs="?", default=0, const=ray.REFILL_DEFAULT, metavar="R",
+                    help="with -orbit -variance: R more passes per frame for the pixels that hold fewer than 1 + R "
+                         f"frames and their neighbours (default R when given without a number: {ray.REFILL_DEFAULT}); "
+                         "prints the refilled pixels per frame")
     ap.add_argument("-ansi", action="store_true",
                     help="render at -s x the terminal size and draw it in the terminal (main.go:86-131)")
     ap.add_argument("-s", type=float, default=4, help="supersampling factor of -ansi")
@@ -83,12 +93,22 @@ def main(argv=None) -> int:
     samples = a.width * a.height * a.r
     if a.orbit < 0 or (a.orbit and (a.passes or a.adaptive)):
         ap.error("-orbit needs N >= 1 and goes with neither -passes nor -adaptive")
+    if (a.variance or a.refill) and not a.orbit:
+        ap.error("-variance and -refill go with -orbit N")
+    if a.refill < 0 or (a.refill and not a.variance):
+        ap.error("-refill needs R >= 0 and -variance")
     if a.orbit:
         cameras = [ray.Orbit(t.Camera, k * a.orbit_step) for k in range(a.orbit)]
-        img = t.RenderSequence(scene, cameras, denoise=a.denoise)[-1]
-        for k, (fresh, age) in enumerate(zip(t.fresh, t.mean_age)):
-            print(f"frame {k}: fresh {fresh / max(a.width * a.height, 1):.4f} mean age {age:.3f}")
-        samples *= a.orbit
+        if a.variance:
+            img = t.RenderSequence(scene, cameras, denoise=a.denoise, variance=True, refill=a.refill)[-1]
+            for k, (fresh, age, n) in enumerate(zip(t.fresh, t.mean_age, t.refilled)):
+                print(f"frame {k}: fresh {fresh / max(a.width * a.height, 1):.4f} mean age {age:.3f} refilled {n}")
+            samples *= t.pixel_passes / max(a.width * a.height, 1)
+        else:
+            img = t.RenderSequence(scene, cameras, denoise=a.denoise)[-1]
+            for k, (fresh, age) in enumerate(zip(t.fresh, t.mean_age)):
+                print(f"frame {k}: fresh {fresh / max(a.width * a.height, 1):.4f} mean age {age:.3f}")
+            samples *= a.orbit
     elif a.adaptive:
         if a.passes <= 0:
             ap.error("-adaptive needs -passes N")

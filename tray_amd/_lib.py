@@ -360,6 +360,28 @@ TEMPORAL_RECORD_DTYPE = np.dtype([("fresh", "<u8"), ("age_sum", "<u8")])
 assert ctypes.sizeof(TemporalState) == 40 and ctypes.sizeof(TemporalParams) == 32
 assert ctypes.sizeof(TemporalRecord) == 16 and TEMPORAL_RECORD_DTYPE.itemsize == 16
 
+# Every symbol include/tray_temporal_variance.h declares (the reprojection step that carries M2 and
+# the variance of listed pixels; in none of the eight lists above).
+TEMPORAL_VARIANCE_EXPORTS = (
+    "tray_temporal_var_version",
+    "tray_temporal_var_step_async",
+    "tray_temporal_var_variance_async",
+)
+
+
+class TemporalVarState(ctypes.Structure):
+    """tray_temporal_var_state: a TemporalState's planes plus m2 (height x width x 3 f64)."""
+    _fields_ = [("colour", ctypes.c_void_p), ("m2", ctypes.c_void_p), ("age", ctypes.c_void_p),
+                ("index", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("width", ctypes.c_int32),
+                ("height", ctypes.c_int32)]
+
+    def adaptive(self) -> "AdaptiveState":
+        """The same planes as a tray_adaptive_state {mean = colour, m2, count = age, width, rows = height}."""
+        return AdaptiveState(self.colour, self.m2, self.age, self.width, self.height)
+
+
+assert ctypes.sizeof(TemporalVarState) == 48
+
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
 DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear", "tray_debug_progress_counts", "tray_debug_plain_instance",
                  "tray_debug_plain_launches")
@@ -491,6 +513,14 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.tray_temporal_step_async.argtypes = [vp, ctypes.POINTER(CameraState), ctypes.POINTER(CameraState),
                                                ctypes.POINTER(TemporalParams), vp, ctypes.POINTER(TemporalState),
                                                ctypes.POINTER(TemporalState), vp, vp]
+    if hasattr(L, "tray_temporal_var_version"):  # include/tray_temporal_variance.h; absent from older builds
+        L.tray_temporal_var_version.restype = i32
+        L.tray_temporal_var_step_async.argtypes = [vp, ctypes.POINTER(CameraState), ctypes.POINTER(CameraState),
+                                                   ctypes.POINTER(TemporalParams), vp,
+                                                   ctypes.POINTER(TemporalVarState),
+                                                   ctypes.POINTER(TemporalVarState), vp, vp, vp]
+        L.tray_temporal_var_variance_async.argtypes = [ctypes.POINTER(TemporalVarState), vp, ctypes.c_int64, vp, i32,
+                                                       vp]
     if hasattr(L, "tray_debug_set"):  # absent from older builds (A/B tools)
         L.tray_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
         L.tray_debug_clear.argtypes = [ctypes.c_char_p]
@@ -909,6 +939,31 @@ def temporal_step_async(scene_handle: int | None, camera: CameraState | None, pr
                                          ctypes.byref(params), frame_ptr,
                                          ctypes.byref(history) if history is not None else None, ctypes.byref(out),
                                          record_ptr, stream))
+
+
+def temporal_var_step_async(scene_handle: int | None, camera: CameraState | None, prev_camera: CameraState | None,
+                            params: TemporalParams, frame_ptr: int | None, history: TemporalVarState | None,
+                            out: TemporalVarState, variance_ptr: int | None = None, record_ptr: int | None = None,
+                            stream: int | None = None, lib_path: str | None = None) -> None:
+    """tray_temporal_var_step_async: temporal_step_async on states that carry m2, with the variance of
+    the mean (height x width x 3 f64, nullable) written in the same launch. Only enqueues on `stream`."""
+    L = lib(lib_path)
+    _raise(L, L.tray_temporal_var_step_async(scene_handle, ctypes.byref(camera) if camera is not None else None,
+                                             ctypes.byref(prev_camera) if prev_camera is not None else None,
+                                             ctypes.byref(params), frame_ptr,
+                                             ctypes.byref(history) if history is not None else None,
+                                             ctypes.byref(out), variance_ptr, record_ptr, stream))
+
+
+def temporal_var_variance_async(state: TemporalVarState, pixels_ptr: int | None, n_pixels: int,
+                                variance_ptr: int | None, device: int = 0, stream: int | None = None,
+                                lib_path: str | None = None) -> None:
+    """tray_temporal_var_variance_async: the variance of the mean of the listed pixels (n_pixels u32;
+    None: every pixel) from the state's m2 and age; unlisted pixels keep their bytes. Only enqueues
+    on `stream`."""
+    L = lib(lib_path)
+    _raise(L, L.tray_temporal_var_variance_async(ctypes.byref(state), pixels_ptr, int(n_pixels), variance_ptr,
+                                                 int(device), stream))
 
 
 def camera_rays_count(params: Params) -> int:

@@ -1215,6 +1215,109 @@ int tray_temporal_step_async(tray_scene_t sc, const tray_camera* cam, const tray
     return TRAY_OK;
 }
 
+// ---- temporal reprojection with M2 (include/tray_temporal_variance.h) --------------
+int32_t tray_temporal_var_version(void) { return TRAY_TEMPORAL_VAR_VERSION; }
+
+int tray_temporal_var_step_async(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
+                                 const tray_temporal_params* tp, const double* frame_device,
+                                 const tray_temporal_var_state* history, const tray_temporal_var_state* out,
+                                 double* variance_device, tray_temporal_record* record_device, void* stream) {
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
+    if (!tp) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params");
+    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null state (out)");
+    if ((history == nullptr) != (prev == nullptr))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "history and prev_camera must both be given or both be null");
+    if (out->width < 0 || out->height < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative width or height");
+    if (history && (history->width != out->width || history->height != out->height))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "history and out differ in width or height");
+    if (tp->max_history < 1 || tp->max_history > (1 << 30))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "max_history must be in 1 .. 2^30");
+    if (tp->flags & ~TRAY_FLAG_LINEAR_SCAN)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "unknown flags (only TRAY_FLAG_LINEAR_SCAN applies)");
+    if (!(std::isfinite(tp->depth_tolerance) && tp->depth_tolerance >= 0.0))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "depth_tolerance must be finite and >= 0");
+    if (!(std::isfinite(tp->snap) && tp->snap >= 0.0 && tp->snap < 0.5))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "snap must be finite, >= 0 and < 0.5");
+    if (tp->reserved != 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "reserved must be 0");
+    const int64_t image = (int64_t)out->width * (int64_t)out->height;
+    if (image > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
+    if (image == 0) return TRAY_OK;
+    // The spans: outputs first (the first n_out; the last two of them nullable), then what is only read.
+    const size_t px = (size_t)image;
+    TemporalSpan spans[13] = {{out->colour, px * 24, 8, "out.colour"},
+                              {out->m2, px * 24, 8, "out.m2"},
+                              {out->age, px * 4, 4, "out.age"},
+                              {out->index, px * 4, 4, "out.index"},
+                              {out->depth, px * 8, 8, "out.depth"},
+                              {variance_device, px * 24, 8, "the variance"},
+                              {record_device, sizeof(tray_temporal_record), 8, "the record"},
+                              {frame_device, px * 24, 8, "the frame"}};
+    const int n_out = 7;
+    int n = 8;
+    if (history) {
+        spans[n++] = {history->colour, px * 24, 8, "history.colour"};
+        spans[n++] = {history->m2, px * 24, 8, "history.m2"};
+        spans[n++] = {history->age, px * 4, 4, "history.age"};
+        spans[n++] = {history->index, px * 4, 4, "history.index"};
+        spans[n++] = {history->depth, px * 8, 8, "history.depth"};
+    }
+    for (int i = 0; i < n; ++i)
+        if (!spans[i].p && i != 5 && i != 6)
+            return fail(TRAY_ERR_INVALID_ARGUMENT, std::string("null buffer: ") + spans[i].name);
+    for (int i = 0; i < n; ++i)
+        if ((uintptr_t)spans[i].p & (spans[i].align - 1))
+            return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(spans[i].name) + " is not " +
+                                                       (spans[i].align == 8 ? "8" : "4") + "-byte aligned");
+    for (int i = 0; i < n_out; ++i)
+        for (int j = i + 1; j < n; ++j)
+            if (spans_overlap(spans[i], spans[j]))
+                return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(spans[i].name) + " overlaps " + spans[j].name);
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    camera_params(cam, k);
+    k.width = out->width;
+    k.height = out->height;
+    k.rows = out->height;
+    TRAY_HIP(hipSetDevice(sc->device));
+    TRAY_HIP(launch_temporal_var_step(k, wants_bvh(sc, tp->flags), sc->bvh_bound, prev, *tp, frame_device, history,
+                                      *out, variance_device, record_device, static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
+int tray_temporal_var_variance_async(const tray_temporal_var_state* state, const uint32_t* pixels_device,
+                                     int64_t n_pixels, double* variance_device, int32_t device, void* stream) {
+    if (!state) return fail(TRAY_ERR_INVALID_ARGUMENT, "null state");
+    if (state->width < 0 || state->height < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative width or height");
+    if (pixels_device && n_pixels < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative n_pixels");
+    const int64_t image = (int64_t)state->width * (int64_t)state->height;
+    if (image > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
+    if (pixels_device && n_pixels > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "n_pixels exceeds 2^31 - 1");
+    if (image == 0 || (pixels_device && n_pixels == 0)) return TRAY_OK;
+    const size_t px = (size_t)image;
+    const TemporalSpan spans[4] = {{variance_device, px * 24, 8, "the variance"},
+                                   {state->m2, px * 24, 8, "m2"},
+                                   {state->age, px * 4, 4, "age"},
+                                   {pixels_device, pixels_device ? (size_t)n_pixels * 4 : 0, 4, "the pixel list"}};
+    for (int i = 0; i < 3; ++i)
+        if (!spans[i].p) return fail(TRAY_ERR_INVALID_ARGUMENT, std::string("null buffer: ") + spans[i].name);
+    for (int i = 0; i < 4; ++i)
+        if ((uintptr_t)spans[i].p & (spans[i].align - 1))
+            return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(spans[i].name) + " is not " +
+                                                       (spans[i].align == 8 ? "8" : "4") + "-byte aligned");
+    for (int j = 1; j < 4; ++j)
+        if (spans_overlap(spans[0], spans[j]))
+            return fail(TRAY_ERR_INVALID_ARGUMENT, std::string("the variance overlaps ") + spans[j].name);
+    const int rc = device_usable(device);
+    if (rc) return rc;
+    TRAY_HIP(hipSetDevice(device));
+    TRAY_HIP(launch_temporal_variance(state->m2, state->age, (uint32_t)image, pixels_device,
+                                      pixels_device ? (uint32_t)n_pixels : 0u, variance_device,
+                                      static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
 // The scene of a slot: its cached upload when the caller passes the same
 // spheres and background as last time (compared byte for byte; the caller's
 // arrays are copied, never retained), else a fresh upload that replaces it.

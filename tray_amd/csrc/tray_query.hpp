@@ -13,6 +13,7 @@
 #include "../../include/tray_aov.h"
 #include "../../include/tray_shade.h"  // includes tray_query.h
 #include "../../include/tray_temporal.h"
+#include "../../include/tray_temporal_variance.h"
 #include "tray_kernel.hpp"
 
 namespace tray {
@@ -76,5 +77,18 @@ hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, cons
                                 const tray_temporal_params& tp, const double* frame,
                                 const tray_temporal_state* history, const tray_temporal_state& out,
                                 tray_temporal_record* record, hipStream_t stream);
+
+// include/tray_temporal_variance.h section 2 (tray_temporal.hip): launch_temporal_step with the
+// M2 planes and the (nullable) variance of the mean.
+hipError_t launch_temporal_var_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
+                                    const tray_temporal_params& tp, const double* frame,
+                                    const tray_temporal_var_state* history, const tray_temporal_var_state& out,
+                                    double* variance, tray_temporal_record* record, hipStream_t stream);
+
+// include/tray_temporal_variance.h section 3 (tray_temporal.hip): the variance of the mean of the
+// n_pixels listed pixels (entries >= image_pixels skipped), or of every pixel when `pixels` is null.
+hipError_t launch_temporal_variance(const double* m2, const int32_t* age, uint32_t image_pixels,
+                                    const uint32_t* pixels, uint32_t n_pixels, double* variance,
+                                    hipStream_t stream);
 
 }  // namespace tray

@@ -1,7 +1,10 @@
 // tray_temporal.hip — include/tray_temporal.h for gfx950: the temporal reprojection
 // step. One launch traces each pixel's centre ray (query_hit, the queries' Scene.Hit),
 // projects the hit into the previous camera, gathers the history there, folds the new
-// frame into it and counts the record's two sums.
+// frame into it and counts the record's two sums. A second instance of the same kernel
+// (include/tray_temporal_variance.h) carries M2 with the colour and writes the variance
+// of the mean in the same launch; a small streaming kernel writes that variance again
+// for a list of pixels, or for the whole frame, after a fold from outside the step.
 //
 // The traversal is tray_query_device.hpp's over tray_device.hpp, the megakernel's own
 // arithmetic; the projection and the fold are plain FP64 in the header's order. Compiled
@@ -17,8 +20,10 @@
 #include <limits>
 
 #include "../../include/tray_temporal.h"
+#include "../../include/tray_temporal_variance.h"
 #include "tray_internal.hpp"
 #include "tray_query_device.hpp"
+#include "tray_stream.hpp"
 
 namespace tray {
 
@@ -45,6 +50,10 @@ struct TemporalArgs {
     double depth_tolerance, snap;
     int32_t max_history;
     uint32_t tiles_x;  // 32 x 8 tiles per row of tiles: ceil(width / 32)
+    // The M2 instance alone (last, so that the plain instance's arguments stay where they were):
+    const double* history_m2;
+    double* out_m2;
+    double* variance;  // nullable
 };
 
 // The kernel's one argument: KernelParams first, where kp_fresh() reads it.
@@ -73,6 +82,10 @@ __host__ __device__ inline double dot3(const double u[3], const double v[3]) {
     return u[0] * v[0] + u[1] * v[1] + u[2] * v[2];
 }
 
+// kM2: the step of include/tray_temporal_variance.h. What it adds reads nothing the plain step
+// decides on and feeds nothing back into it, so colour, age, index, depth and the record are
+// the plain instance's.
+template <bool kM2>
 __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaunch L) {
     __shared__ unsigned long long red[2][kQueryBlock / 64];
     const KernelParams& p = L.p;
@@ -103,6 +116,7 @@ __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaun
         a.out.depth[pix] = t;
         const double* xin = a.frame + pix * 3;
         D3 colour = d3(xin[0], xin[1], xin[2]);
+        D3 m2 = d3(0, 0, 0);  // kM2: out.m2, 0.0 for a fresh pixel
         fresh = true;
         age = 1;
         if (a.history.colour) {
@@ -124,7 +138,7 @@ __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaun
                 const int64_t ix0 = (int64_t)x0, iy0 = (int64_t)y0;  // in [-1, width] x [-1, height]: in range
                 const double bound = a.depth_tolerance * z;
                 double W = 0.0;
-                D3 H = d3(0, 0, 0);
+                D3 H = d3(0, 0, 0), M = d3(0, 0, 0);
                 int32_t A = std::numeric_limits<int32_t>::max();
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -140,6 +154,10 @@ __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaun
                     W = W + w[j];
                     H = d3(H.x + w[j] * c0x, H.y + w[j] * c1, H.z + w[j] * c2);
                     A = ha < A ? ha : A;
+                    if constexpr (kM2) {
+                        const double* m = a.history_m2 + q * 3;
+                        M = d3(M.x + w[j] * m[0], M.y + w[j] * m[1], M.z + w[j] * m[2]);
+                    }
                 }
                 // e. the fold
                 if (W > 0.0) {
@@ -147,8 +165,17 @@ __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaun
                     const int32_t cap = a.max_history - 1;
                     const int32_t k = (A < cap ? A : cap) + 1;
                     const double dk = (double)k;
+                    const D3 X = colour;
                     colour = d3(hm.x + (colour.x - hm.x) / dk, hm.y + (colour.y - hm.y) / dk,
                                 hm.z + (colour.z - hm.z) / dk);
+                    if constexpr (kM2) {
+                        // the gathered M2, scaled to a history of n0 = k - 1 samples, then Welford's update
+                        D3 m = sdiv(M, W);
+                        const int32_t n0 = k - 1;
+                        if (A > n0) m = smul(m, (double)(n0 - 1) / (double)(A - 1));
+                        m2 = d3(m.x + (X.x - hm.x) * (X.x - colour.x), m.y + (X.y - hm.y) * (X.y - colour.y),
+                                m.z + (X.z - hm.z) * (X.z - colour.z));
+                    }
                     age = k;
                     fresh = false;
                 }
@@ -157,6 +184,19 @@ __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaun
         double* co = a.out.colour + pix * 3;
         co[0] = colour.x, co[1] = colour.y, co[2] = colour.z;
         a.out.age[pix] = age;
+        if constexpr (kM2) {
+            double* mo = a.out_m2 + pix * 3;
+            mo[0] = m2.x, mo[1] = m2.y, mo[2] = m2.z;
+            if (a.variance) {
+                double* vo = a.variance + pix * 3;
+                if (age < 2) {
+                    vo[0] = vo[1] = vo[2] = __builtin_inf();
+                } else {
+                    const double D = (double)age * (double)(age - 1);
+                    vo[0] = m2.x / D, vo[1] = m2.y / D, vo[2] = m2.z / D;
+                }
+            }
+        }
     }
     // The record: a wave reduction, then one atomic add per workgroup and sum.
     tray_temporal_record* const record = L.a.record;
@@ -177,10 +217,11 @@ __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaun
     }
 }
 
-hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
-                                const tray_temporal_params& tp, const double* frame,
-                                const tray_temporal_state* history, const tray_temporal_state& out,
-                                tray_temporal_record* record, hipStream_t stream) {
+// The launch of either instance: m2_out null is the plain step.
+static hipError_t launch_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
+                              const tray_temporal_params& tp, const double* frame, const tray_temporal_state* history,
+                              const double* history_m2, const tray_temporal_state& out, double* out_m2,
+                              double* variance, tray_temporal_record* record, hipStream_t stream) {
     if (out.width <= 0 || out.height <= 0) return hipSuccess;
     size_t lds = 0;
     QueryArgs q = query_args(p, use_bvh, bound, nullptr, 0, lds);
@@ -195,8 +236,11 @@ hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, cons
     a.depth_tolerance = tp.depth_tolerance;
     a.snap = tp.snap;
     a.max_history = tp.max_history;
+    a.out_m2 = out_m2;
+    a.variance = variance;
     if (history && prev && tp.max_history > 1) {  // max_history 1: the frame itself (the header, section 3)
         a.history = *history;
+        a.history_m2 = history_m2;
         PrevCamera& P = a.prev;
         for (int c = 0; c < 3; ++c) {
             P.position[c] = prev->position[c];
@@ -214,8 +258,106 @@ hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, cons
     hipError_t e = hipSuccess;
     if (record) e = hipMemsetAsync(record, 0, sizeof(*record), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(temporal_step_kernel, dim3(a.tiles_x * tiles_y), dim3(kQueryBlock), lds, stream,
-                       TemporalLaunch{p, q, a});
+    if (out_m2)
+        hipLaunchKernelGGL(temporal_step_kernel<true>, dim3(a.tiles_x * tiles_y), dim3(kQueryBlock), lds, stream,
+                           TemporalLaunch{p, q, a});
+    else
+        hipLaunchKernelGGL(temporal_step_kernel<false>, dim3(a.tiles_x * tiles_y), dim3(kQueryBlock), lds, stream,
+                           TemporalLaunch{p, q, a});
+    return hipGetLastError();
+}
+
+hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
+                                const tray_temporal_params& tp, const double* frame,
+                                const tray_temporal_state* history, const tray_temporal_state& out,
+                                tray_temporal_record* record, hipStream_t stream) {
+    return launch_step(p, use_bvh, bound, prev, tp, frame, history, nullptr, out, nullptr, nullptr, record, stream);
+}
+
+static tray_temporal_state plain_state(const tray_temporal_var_state& s) {
+    return tray_temporal_state{s.colour, s.age, s.index, s.depth, s.width, s.height};
+}
+
+hipError_t launch_temporal_var_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
+                                    const tray_temporal_params& tp, const double* frame,
+                                    const tray_temporal_var_state* history, const tray_temporal_var_state& out,
+                                    double* variance, tray_temporal_record* record, hipStream_t stream) {
+    tray_temporal_state h{};
+    if (history) h = plain_state(*history);
+    return launch_step(p, use_bvh, bound, prev, tp, frame, history ? &h : nullptr, history ? history->m2 : nullptr,
+                       plain_state(out), out.m2, variance, record, stream);
+}
+
+// ---- include/tray_temporal_variance.h section 3: the variance of the mean from (m2, age) ----
+//
+// Streaming, 32 bytes read and 24 written per pixel. The whole frame is read and written in
+// tray_stream.hpp's pattern (a wave covers 1 KiB of consecutive bytes per instruction), each
+// element dividing by the D of pixel e / 3 from a gathered age, as the selection's metric pass
+// does. A list is one entry per lane: its pixel's 3 + 1 values gathered, 3 scattered.
+struct VarianceArgs {
+    const double* m2;
+    const int32_t* age;
+    const uint32_t* pixels;  // null: every pixel
+    double* variance;
+    size_t elems, chunks;    // whole frame: image_pixels x 3 doubles in chunks of kBlockElems
+    uint32_t n_pixels, image_pixels;
+};
+
+__device__ __forceinline__ double variance_of_mean(double m2, int32_t n) {
+    if (n < 2) return __builtin_inf();
+    return m2 / ((double)n * (double)(n - 1));
+}
+
+__global__ __launch_bounds__(kThreads) void temporal_variance_frame_kernel(const VarianceArgs A) {
+    const int lane = (int)threadIdx.x % kWave, wave = (int)threadIdx.x / kWave;
+    for (size_t chunk = blockIdx.x; chunk < A.chunks; chunk += gridDim.x) {
+        const size_t wave_base = chunk * kBlockElems + (size_t)wave * kWaveElems;
+#pragma unroll
+        for (int j = 0; j < kSlots; ++j) {
+            const size_t at = wave_base + (size_t)j * kRowElems + 2 * (size_t)lane;
+            if (at >= A.elems) continue;
+            double m0 = 0.0, m1 = 0.0;
+            load_pair(A.m2, at, A.elems, m0, m1);
+            const double v0 = variance_of_mean(m0, A.age[at / 3]);
+            const double v1 = at + 1 < A.elems ? variance_of_mean(m1, A.age[(at + 1) / 3]) : 0.0;
+            store_pair(A.variance, at, A.elems, v0, v1);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void temporal_variance_list_kernel(const VarianceArgs A) {
+    const uint32_t i = blockIdx.x * (uint32_t)kThreads + threadIdx.x;
+    if (i >= A.n_pixels) return;
+    const uint32_t pix = A.pixels[i];
+    if (pix >= A.image_pixels) return;  // a bad entry is skipped
+    const int32_t n = A.age[pix];
+    const double* m = A.m2 + (size_t)pix * 3;
+    double* v = A.variance + (size_t)pix * 3;
+    const double m0 = m[0], m1 = m[1], m2 = m[2];
+    v[0] = variance_of_mean(m0, n), v[1] = variance_of_mean(m1, n), v[2] = variance_of_mean(m2, n);
+}
+
+hipError_t launch_temporal_variance(const double* m2, const int32_t* age, uint32_t image_pixels,
+                                    const uint32_t* pixels, uint32_t n_pixels, double* variance,
+                                    hipStream_t stream) {
+    VarianceArgs a{};
+    a.m2 = m2;
+    a.age = age;
+    a.pixels = pixels;
+    a.variance = variance;
+    a.image_pixels = image_pixels;
+    if (pixels) {
+        if (n_pixels == 0 || image_pixels == 0) return hipSuccess;
+        a.n_pixels = n_pixels;
+        const uint32_t blocks = (n_pixels + (uint32_t)kThreads - 1u) / (uint32_t)kThreads;  // <= 2^23
+        hipLaunchKernelGGL(temporal_variance_list_kernel, dim3(blocks), dim3(kThreads), 0, stream, a);
+    } else {
+        if (image_pixels == 0) return hipSuccess;
+        a.elems = (size_t)image_pixels * 3;
+        a.chunks = (a.elems + kBlockElems - 1) / kBlockElems;
+        const int64_t grid = (int64_t)a.chunks < kMaxGrid ? (int64_t)a.chunks : kMaxGrid;
+        hipLaunchKernelGGL(temporal_variance_frame_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, stream, a);
+    }
     return hipGetLastError();
 }
 

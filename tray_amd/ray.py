@@ -354,6 +354,7 @@ def Orbit(camera: Camera, degrees: float) -> Camera:
 
 
 ORBIT_STEP_DEGREES = 1.0  # the CLI's default -orbit-step (tools/temporal_sweep.py)
+REFILL_DEFAULT = 3  # the CLI's -refill without a number (tools/temporal_variance_sweep.py)
 
 # --------------------------------------------------------------------- tracer
 _CAMERA_FIELDS = ("Position", "LookAt", "Up", "VerticalFoV", "FocalLength", "FocusDistance", "Aperture")
@@ -845,7 +846,9 @@ class Tracer:  # ray/tracer.go:25-36
         self.imageData[:] = rgba.cpu().numpy()
         return self.imageData
 
-    def RenderSequence(self, scene: Scene | None, cameras, denoise: bool = False, **overrides) -> list:
+    def RenderSequence(self, scene: Scene | None, cameras, denoise: bool = False, variance: bool = False,
+                       refill: int = 0, refill_tolerance: float = 1e150, refill_dilate: int = 1,
+                       **overrides) -> list:
         """A moving camera that keeps what it has seen (include/tray_temporal.h): frame k is rendered
         through cameras[k] (a sequence of Camera objects, each initialized here for the tracer's size
         as Render does) as progressive pass k of the tracer's one seed, so a still camera sees
@@ -855,12 +858,45 @@ class Tracer:  # ray/tracer.go:25-36
         tray_render_aov_async) and the sRGB encoding are enqueued on one stream over two ping-pong
         states; nothing is read back before the last frame is enqueued.
 
+        variance=True (include/tray_temporal_variance.h) runs tray_temporal_var_step_async instead:
+        the states carry M2, the colour, ages and records are the same bits, `variance` keeps the
+        last frame's (H, W, 3) variance of the mean and `m2` its M2, and denoise=True then means the
+        variance-guided filter (tray_denoise_variance_async on the step's variance) in place of the
+        plain one, which damages a pixel that holds many samples. With either filter `filtered`
+        keeps the last frame as shown, (H, W, 3) FP64, before the sRGB encoding.
+
+        refill=R > 0 implies variance=True and spends R more passes per frame on the pixels that
+        hold fewer than 1 + R frames (the fresh ones: disocclusions, the frame's leading edge and all
+        of frame 0) and, with refill_dilate 1, on their 8 neighbours: tray_adaptive_select_async on
+        the state as a tray_adaptive_state (min_passes 1 + R, max_passes max_history), a 32-byte
+        readback of its record for the list's length, tray_render_pixels_async,
+        tray_adaptive_fold_async and tray_temporal_var_variance_async over the list. Frame k then
+        owns the progressive passes k (1 + R) .. (k + 1)(1 + R) - 1: the uniform frame is the
+        first, the refill the rest, so no sample repeats. refill_tolerance is the selection's
+        tolerance; at the default 1e150 only the count decides. A real tolerance (0.05, say)
+        refills by variance, which selects most of an r = 4 frame: a list renderer breaks even with
+        the whole-frame renderer at an active fraction of about 0.18, so that is
+        rarely worth it. `refilled` holds the per-frame list lengths, `pixel_passes` the passes
+        spent in all (H x W per frame plus R per listed pixel); `age` and `linear` include the refill,
+        `fresh` and `mean_age` are the step's records, before it.
+
         overrides: fields of tray_temporal_params (max_history, depth_tolerance, snap, flags).
         Returns the list of (H, W, 4) uint8 RGBA frames and keeps the last in imageData; `linear`
         holds the last accumulated FP64 frame (before the filter), `age` its (H, W) int32 ages, `fresh`
         and `mean_age` the per-frame lists from the records (fresh pixels; the mean output age).
-        ValueError for an empty sequence, an entry that is not a Camera or an unknown override, before
-        any device work. No Go counterpart."""
+        ValueError for an empty sequence, an entry that is not a Camera, an unknown override, a
+        refill that is not an integer >= 0 or exceeds max_history - 1 (a pixel could never hold
+        1 + R frames), a refill_tolerance that is not finite, >= 0 and of finite square, or a
+        refill_dilate other than 0 or 1, before any device work. No Go counterpart."""
+        if isinstance(refill, bool) or not isinstance(refill, (int, np.integer)) or refill < 0:
+            raise ValueError("refill must be an integer >= 0")
+        refill = int(refill)
+        if refill_dilate not in (0, 1):
+            raise ValueError("refill_dilate must be 0 or 1")
+        rt = float(refill_tolerance)
+        if not (rt >= 0.0 and rt * rt < float("inf")):
+            raise ValueError("refill_tolerance must be finite and >= 0, with a finite square")
+        variance = bool(variance) or refill > 0
         cameras = list(cameras) if cameras is not None else []
         if not cameras:
             raise ValueError("cameras must hold at least one Camera")
@@ -870,6 +906,9 @@ class Tracer:  # ray/tracer.go:25-36
         if unknown or "reserved" in overrides:
             raise ValueError(f"unknown temporal parameters {unknown or ['reserved']}")
         tp = _lib.temporal_params(**overrides)
+        if refill and tp.max_history < 1 + refill:
+            raise ValueError(f"refill={refill} needs max_history >= {1 + refill}: no pixel could hold "
+                             f"1 + refill frames (max_history is {tp.max_history})")
         import torch
 
         scene = self._apply_defaults(scene)
@@ -882,6 +921,10 @@ class Tracer:  # ray/tracer.go:25-36
         self.seed = self._seed()  # once: every frame is a pass of this stream
         self.age = np.zeros((h, w), dtype=np.int32)
         self.fresh, self.mean_age = [], []
+        if variance:
+            self.variance = np.full((h, w, 3), np.inf)
+            self.m2 = np.zeros((h, w, 3))
+            self.refilled, self.pixel_passes = [], 0
         if h * w == 0:
             return [self.imageData.copy() for _ in cameras]
         stream = torch.cuda.current_stream(where).cuda_stream
@@ -891,6 +934,10 @@ class Tracer:  # ray/tracer.go:25-36
         def planes():
             t = dict(colour=torch.empty((h, w, 3), **f64), age=torch.empty((h, w), dtype=torch.int32, device=where),
                      index=torch.empty((h, w), dtype=torch.int32, device=where), depth=torch.empty((h, w), **f64))
+            if variance:
+                t["m2"] = torch.empty((h, w, 3), **f64)
+                return t, _lib.TemporalVarState(t["colour"].data_ptr(), t["m2"].data_ptr(), t["age"].data_ptr(),
+                                                t["index"].data_ptr(), t["depth"].data_ptr(), w, h)
             return t, _lib.TemporalState(t["colour"].data_ptr(), t["age"].data_ptr(), t["index"].data_ptr(),
                                          t["depth"].data_ptr(), w, h)
 
@@ -902,23 +949,72 @@ class Tracer:  # ray/tracer.go:25-36
         if denoise:
             aov = {name: torch.empty((h, w, 3)[: 3 if ch > 1 else 2], **f64)
                    for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1))}
+        var_plane = torch.empty((h, w, 3), **f64) if variance else None
+        if refill:
+            ap = _lib.adaptive_params(tolerance=rt, min_passes=1 + refill, max_passes=int(tp.max_history),
+                                      dilate=int(refill_dilate))
+            nbytes = _lib.adaptive_workspace_bytes(w, h)
+            work = torch.empty((nbytes // 8,), **f64)
+            active = torch.empty((h * w,), dtype=torch.int32, device=where)
+            arecord = torch.empty((4,), **f64)
+            values = torch.empty((refill * h * w * 3,), **f64)  # frame 0 lists every pixel
+        if denoise and variance:
+            dp = _lib.denoise_variance_params(w, h)
+            dbytes = _lib.denoise_variance_workspace_bytes(dp)
+            dwork = torch.empty((max(dbytes, 8) // 8,), **f64)
+            filtered = torch.empty((h, w, 3), **f64)
+        stride = 1 + refill  # frame k owns the passes k * stride .. (k + 1) * stride - 1
         for k, cam in enumerate(cameras):
             params = _lib.make_params(w, h, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, self.seed, 0, h,
-                                      pass_=k)
+                                      pass_=k * stride)
             dev.render_async(cam._state, params, frame.data_ptr(), None, stream)
             out = states[k & 1]
-            _lib.temporal_step_async(dev.handle, cam._state, cameras[k - 1]._state if k else None, tp,
-                                     frame.data_ptr(), states[(k - 1) & 1][1] if k else None, out[1],
-                                     records[k].data_ptr(), stream)
+            if variance:
+                _lib.temporal_var_step_async(dev.handle, cam._state, cameras[k - 1]._state if k else None, tp,
+                                             frame.data_ptr(), states[(k - 1) & 1][1] if k else None, out[1],
+                                             var_plane.data_ptr(), records[k].data_ptr(), stream)
+            else:
+                _lib.temporal_step_async(dev.handle, cam._state, cameras[k - 1]._state if k else None, tp,
+                                         frame.data_ptr(), states[(k - 1) & 1][1] if k else None, out[1],
+                                         records[k].data_ptr(), stream)
+            if refill:
+                ast = out[1].adaptive()
+                _lib.adaptive_select_async(ast, ap, active.data_ptr(), arecord.data_ptr(), work.data_ptr(), nbytes,
+                                           None, device, stream)
+                n_active = int(arecord.cpu().numpy().view(_lib.ADAPTIVE_RECORD_DTYPE)[0]["n_active"])  # 32 bytes
+                self.refilled.append(n_active)
+                if n_active:
+                    rp = _lib.make_params(w, h, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, self.seed, 0, h,
+                                          pass_=k * stride + 1)
+                    dev.render_pixels_async(cam._state, rp, active.data_ptr(), n_active, values.data_ptr(), refill,
+                                            stream=stream)
+                    _lib.adaptive_fold_async(ast, active.data_ptr(), n_active, values.data_ptr(), refill, device,
+                                             stream)
+                    _lib.temporal_var_variance_async(out[1], active.data_ptr(), n_active, var_plane.data_ptr(),
+                                                     device, stream)
             shown = out[0]["colour"]
             if denoise:
                 dev.render_aov_async(cam._state, params, aov["albedo"].data_ptr(), aov["normal"].data_ptr(),
                                      aov["depth"].data_ptr(), stream=stream)
-                shown = self._denoise_device(torch, shown, aov, {})
+                if variance:
+                    _lib.denoise_variance_async(shown.data_ptr(), var_plane.data_ptr(), dp, filtered.data_ptr(),
+                                                dwork.data_ptr() if dbytes else None, dbytes,
+                                                aov["albedo"].data_ptr(), aov["normal"].data_ptr(),
+                                                aov["depth"].data_ptr(), device=device, stream=stream)
+                    shown = filtered
+                else:
+                    shown = self._denoise_device(torch, shown, aov, {})
             _lib.linear_to_srgba_async(shown.data_ptr(), h * w, rgba[k].data_ptr(), device, stream)
         last = states[(len(cameras) - 1) & 1][0]
+        if denoise:
+            self.filtered = shown.cpu().numpy()  # the last frame as shown, before the sRGB encoding
         self.linear[:] = last["colour"].cpu().numpy()
         self.age = last["age"].cpu().numpy()
+        if variance:
+            self.variance = var_plane.cpu().numpy()
+            self.m2 = last["m2"].cpu().numpy()
+            self.refilled = self.refilled if refill else [0] * len(cameras)
+            self.pixel_passes = h * w * len(cameras) + refill * sum(self.refilled)
         rec = records.cpu().numpy()
         self.fresh = [int(r[0]) for r in rec]
         self.mean_age = [float(r[1]) / (h * w) for r in rec]
