@@ -15,9 +15,9 @@ import pytest
 import adaptive_ref as A
 import progressive_ref as R
 from conftest import DEFAULT_BG, RICH_SETUP, ROOT
-from test_gpu_denoise import assert_same_bits, book_frame
+from test_gpu_denoise import assert_same_bits, book_frame, device_denoise
 from test_gpu_parity import bg_struct, camera
-from test_gpu_progressive import Fold, Guarded, _tracer, device_passes
+from test_gpu_progressive import Fold, Guarded, _tracer, device_filter, device_passes
 from test_gpu_query import bits, rich2, torch  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -383,6 +383,87 @@ def test_render_adaptive_pixels_hold_the_uniform_state_of_their_counts(L, torch,
     plain = t.linear.copy()
     t.RenderAdaptive(scene, max_passes, min_passes=4, batch=4, tolerance=0.0, denoise=True)
     assert np.isfinite(t.linear).all() and not np.array_equal(t.linear, plain)
+
+
+# ------------------------------------- 4b. the filter and the guides behind the Tracer --
+PINNED = dict(max_passes=8, min_passes=4, batch=4, tolerance=0.0)  # 48 x 27, r = 4, seed 2
+
+
+def srgba(L, linear):
+    linear = np.ascontiguousarray(linear)
+    out = np.zeros(linear.shape[:2] + (4,), dtype=np.uint8)
+    L.check(L.lib().tray_to_srgba(linear.ctypes.data, linear.shape[0] * linear.shape[1], out.ctypes.data))
+    return out
+
+
+@pytest.fixture(scope="module")
+def unfiltered(L, torch, rich2):
+    """RenderAdaptive and RenderProgressive without the filter, and RenderAOV's buffers: what the
+    filtered calls below must be the composition of. Computed once and left unchanged."""
+    ray, t = _tracer(48, 27, 4)
+    scene = ray.Scene.from_array(rich2)
+    t.RenderAdaptive(scene, **PINNED)
+    adaptive = (t.linear.copy(), t.variance.copy())
+    t.RenderProgressive(scene, 4, batch=4, tolerance=0.0)
+    progressive = (t.linear.copy(), t.variance.copy())
+    aov = t.RenderAOV(scene)
+    assert np.isfinite(adaptive[1]).all() and np.isfinite(progressive[1]).all()
+    return dict(scene=scene, adaptive=adaptive, progressive=progressive,
+                guides={k: aov[k] for k in ("albedo", "normal", "depth")})
+
+
+def test_render_adaptive_denoised_equals_the_composition(L, torch, unfiltered):
+    """RenderAdaptive(denoise=True) is tray_denoise_variance_async over the `linear` and `variance` of
+    the same call without the filter, guided by RenderAOV's buffers, then tray_to_srgba: bit for bit,
+    with the tracer's own guides, with the caller's, and with an override."""
+    mean, variance = unfiltered["adaptive"]
+    g = unfiltered["guides"]
+    want, _ = device_filter(L, torch, mean, variance, g["albedo"], g["normal"], g["depth"])
+    assert not np.array_equal(want, mean)
+    _, t = _tracer(48, 27, 4)
+    got = t.RenderAdaptive(unfiltered["scene"], denoise=True, **PINNED).copy()
+    assert_same_bits(t.linear, want, "RenderAdaptive(denoise=True): linear")
+    assert_same_bits(t.variance, variance, "RenderAdaptive(denoise=True): variance")
+    assert np.array_equal(got, srgba(L, want))
+    again = t.RenderAdaptive(unfiltered["scene"], denoise=True, guides=g, **PINNED)
+    assert np.array_equal(again, got)
+    assert_same_bits(t.linear, want, "RenderAdaptive(guides=RenderAOV's): linear")
+    half = L.denoise_variance_params(48, 27).sigma_variance / 2
+    other, _ = device_filter(L, torch, mean, variance, g["albedo"], g["normal"], g["depth"], sigma_variance=half)
+    t.RenderAdaptive(unfiltered["scene"], denoise=True, sigma_variance=half, **PINNED)
+    assert_same_bits(t.linear, other, "RenderAdaptive(sigma_variance=half the default): linear")
+    assert np.array_equal(t.imageData, srgba(L, other))
+    assert not np.array_equal(bits(other), bits(want))
+
+
+def test_guides_without_depth_give_the_c_call_with_a_null_depth(L, torch, unfiltered):
+    g = {k: unfiltered["guides"][k] for k in ("albedo", "normal")}
+    _, t = _tracer(48, 27, 4)
+    mean, variance = unfiltered["adaptive"]
+    assert_same_bits(t.Denoise(mean, g), device_denoise(L, torch, mean, g["albedo"], g["normal"], None),
+                     "Denoise without depth")
+    want, _ = device_filter(L, torch, mean, variance, g["albedo"], g["normal"], None)
+    full, _ = device_filter(L, torch, mean, variance, **unfiltered["guides"])
+    assert not np.array_equal(bits(want), bits(full))  # the depth term matters here
+    t.RenderAdaptive(unfiltered["scene"], denoise=True, guides=g, **PINNED)
+    assert_same_bits(t.linear, want, "RenderAdaptive without depth")
+    assert np.array_equal(t.imageData, srgba(L, want))
+    mean, variance = unfiltered["progressive"]
+    want, _ = device_filter(L, torch, mean, variance, g["albedo"], g["normal"], None)
+    t.RenderProgressive(unfiltered["scene"], 4, batch=4, tolerance=0.0, denoise=True, guides=g)
+    assert_same_bits(t.linear, want, "RenderProgressive without depth")
+    assert np.array_equal(t.imageData, srgba(L, want))
+
+
+def test_a_guide_of_the_wrong_shape_is_refused(L, torch, unfiltered):
+    g = dict(unfiltered["guides"], albedo=np.zeros((27, 48)))
+    _, t = _tracer(48, 27, 4)
+    with pytest.raises(ValueError):
+        t.Denoise(unfiltered["adaptive"][0], g)
+    with pytest.raises(ValueError):
+        t.RenderProgressive(unfiltered["scene"], 4, batch=4, tolerance=0.0, denoise=True, guides=g)
+    with pytest.raises(ValueError):
+        t.RenderAdaptive(unfiltered["scene"], denoise=True, guides=g, **PINNED)
 
 
 # ------------------------------------------------------------------ 5. conditions --

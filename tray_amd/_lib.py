@@ -767,25 +767,32 @@ def linear_to_srgba_async(rgb_ptr: int, n_pixels: int, rgba_ptr: int, device: in
     check(lib().tray_linear_to_srgba_async(rgb_ptr, n_pixels, rgba_ptr, device, stream))
 
 
+def _raise(L, rc: int) -> None:
+    if rc != TRAY_OK:
+        raise TrayError(rc, L.tray_last_error().decode())
+
+
+def _override(p, overrides: dict, noun: str):
+    """The parameter struct `p` with fields set by name; ValueError for a name it does not have."""
+    for name, value in overrides.items():
+        if name not in dict(type(p)._fields_):
+            raise ValueError(f"unknown {noun} parameter {name!r}")
+        setattr(p, name, value)
+    return p
+
+
 def denoise_params(width: int, rows: int, lib_path: str | None = None, **overrides) -> DenoiseParams:
     """tray_denoise_default_params for a width x rows image, with fields overridden by name."""
     p = DenoiseParams()
     L = lib(lib_path)
-    if L.tray_denoise_default_params(int(width), int(rows), ctypes.byref(p)) != TRAY_OK:
-        raise TrayError(TRAY_ERR_INVALID_ARGUMENT, L.tray_last_error().decode())
-    for name, value in overrides.items():
-        if name not in dict(DenoiseParams._fields_):
-            raise ValueError(f"unknown denoise parameter {name!r}")
-        setattr(p, name, value)
-    return p
+    _raise(L, L.tray_denoise_default_params(int(width), int(rows), ctypes.byref(p)))
+    return _override(p, overrides, "denoise")
 
 
 def denoise_workspace_bytes(params: DenoiseParams, lib_path: str | None = None) -> int:
     n = ctypes.c_size_t(0)
     L = lib(lib_path)
-    rc = L.tray_denoise_workspace_bytes(ctypes.byref(params), ctypes.byref(n))
-    if rc != TRAY_OK:
-        raise TrayError(rc, L.tray_last_error().decode())
+    _raise(L, L.tray_denoise_workspace_bytes(ctypes.byref(params), ctypes.byref(n)))
     return int(n.value)
 
 
@@ -797,15 +804,8 @@ def denoise_async(colour_ptr: int, params: DenoiseParams, out_ptr: int, workspac
     (rows x width x 3 f64 in and out; a None guide drops its term). Only enqueues on `stream`."""
     guides = DenoiseGuides(albedo_ptr, normal_ptr, depth_ptr)
     L = lib(lib_path)
-    rc = L.tray_denoise_async(colour_ptr, ctypes.byref(guides), ctypes.byref(params), out_ptr, workspace_ptr,
-                              int(workspace_bytes), int(device), stream)
-    if rc != TRAY_OK:
-        raise TrayError(rc, L.tray_last_error().decode())
-
-
-def _raise(L, rc: int) -> None:
-    if rc != TRAY_OK:
-        raise TrayError(rc, L.tray_last_error().decode())
+    _raise(L, L.tray_denoise_async(colour_ptr, ctypes.byref(guides), ctypes.byref(params), out_ptr, workspace_ptr,
+                                   int(workspace_bytes), int(device), stream))
 
 
 def accum_metric_params(lib_path: str | None = None, **overrides) -> AccumMetricParams:
@@ -813,11 +813,7 @@ def accum_metric_params(lib_path: str | None = None, **overrides) -> AccumMetric
     p = AccumMetricParams()
     L = lib(lib_path)
     _raise(L, L.tray_accum_metric_default_params(ctypes.byref(p)))
-    for name, value in overrides.items():
-        if name not in dict(AccumMetricParams._fields_):
-            raise ValueError(f"unknown metric parameter {name!r}")
-        setattr(p, name, value)
-    return p
+    return _override(p, overrides, "metric")
 
 
 def accum_fold_async(acc: Accum, frames_ptr: int | None, n_frames: int, device: int = 0, stream: int | None = None,
@@ -844,11 +840,7 @@ def denoise_variance_params(width: int, rows: int, lib_path: str | None = None, 
     p = DenoiseVarianceParams()
     L = lib(lib_path)
     _raise(L, L.tray_denoise_variance_default_params(int(width), int(rows), ctypes.byref(p)))
-    for name, value in overrides.items():
-        if name not in dict(DenoiseVarianceParams._fields_):
-            raise ValueError(f"unknown variance-guided denoise parameter {name!r}")
-        setattr(p, name, value)
-    return p
+    return _override(p, overrides, "variance-guided denoise")
 
 
 def denoise_variance_workspace_bytes(params: DenoiseVarianceParams, lib_path: str | None = None) -> int:
@@ -878,11 +870,7 @@ def adaptive_params(lib_path: str | None = None, **overrides) -> AdaptiveParams:
     p = AdaptiveParams()
     L = lib(lib_path)
     _raise(L, L.tray_adaptive_default_params(ctypes.byref(p)))
-    for name, value in overrides.items():
-        if name not in dict(AdaptiveParams._fields_):
-            raise ValueError(f"unknown adaptive parameter {name!r}")
-        setattr(p, name, value)
-    return p
+    return _override(p, overrides, "adaptive")
 
 
 def adaptive_workspace_bytes(width: int, rows: int, lib_path: str | None = None) -> int:
@@ -918,11 +906,7 @@ def temporal_params(lib_path: str | None = None, **overrides) -> TemporalParams:
     p = TemporalParams()
     L = lib(lib_path)
     _raise(L, L.tray_temporal_default_params(ctypes.byref(p)))
-    for name, value in overrides.items():
-        if name not in dict(TemporalParams._fields_):
-            raise ValueError(f"unknown temporal parameter {name!r}")
-        setattr(p, name, value)
-    return p
+    return _override(p, overrides, "temporal")
 
 
 def temporal_step_async(scene_handle: int | None, camera: CameraState | None, prev_camera: CameraState | None,

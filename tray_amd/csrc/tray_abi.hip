@@ -22,7 +22,7 @@
 #include "../../include/tray.h"
 #include "../../include/tray_adaptive.h"
 #include "../../include/tray_debug.h"
-#include "tray_internal.hpp"
+#include "tray_check.hpp"
 #include "bvh.hpp"
 #include "rng.hpp"
 #include "tray_kernel.hpp"
@@ -944,7 +944,7 @@ int tray_render_stats_async(tray_scene_t sc, const tray_camera* cam, const tray_
 // ---- ray queries (include/tray_query.h) ----------------------------------------
 int32_t tray_query_version(void) { return TRAY_QUERY_VERSION; }
 
-constexpr int64_t kQueryMaxRays = 0x7FFFFFFF;  // ray indices are 32-bit on the device
+constexpr int64_t kQueryMaxRays = kMaxPixels;  // ray indices are 32-bit on the device
 
 // The checks the scene queries share, before any device work.
 static int validate_query(tray_scene_t sc, const void* rays, int64_t n, int32_t flags, const void* out) {
@@ -1138,23 +1138,12 @@ int tray_temporal_default_params(tray_temporal_params* out) {
     return TRAY_OK;
 }
 
-namespace {
-struct TemporalSpan {
-    const void* p;
-    size_t bytes;
-    uintptr_t align;
-    const char* name;
-};
-bool spans_overlap(const TemporalSpan& a, const TemporalSpan& b) {
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a.p && b.p && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-}  // namespace
-
-int tray_temporal_step_async(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
-                             const tray_temporal_params* tp, const double* frame_device,
-                             const tray_temporal_state* history, const tray_temporal_state* out,
-                             tray_temporal_record* record_device, void* stream) {
+// Both steps (the plain one without the M2 and variance rows): the states come as
+// tray_temporal_var_state, a plain state widened with a null m2.
+static int temporal_step(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
+                         const tray_temporal_params* tp, const double* frame_device,
+                         const tray_temporal_var_state* history, const tray_temporal_var_state* out, bool with_m2,
+                         double* variance_device, tray_temporal_record* record_device, void* stream) {
     if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
     if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
     if (!tp) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params");
@@ -1174,34 +1163,37 @@ int tray_temporal_step_async(tray_scene_t sc, const tray_camera* cam, const tray
         return fail(TRAY_ERR_INVALID_ARGUMENT, "snap must be finite, >= 0 and < 0.5");
     if (tp->reserved != 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "reserved must be 0");
     const int64_t image = (int64_t)out->width * (int64_t)out->height;
-    if (image > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
+    if (image > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
     if (image == 0) return TRAY_OK;
-    // The spans: outputs first (the first n_out), then what is only read.
+    // The spans: outputs first (the first n_out; the variance and the record nullable), then what is only read.
     const size_t px = (size_t)image;
-    TemporalSpan spans[10] = {{out->colour, px * 24, 8, "out.colour"},
-                              {out->age, px * 4, 4, "out.age"},
-                              {out->index, px * 4, 4, "out.index"},
-                              {out->depth, px * 8, 8, "out.depth"},
-                              {record_device, sizeof(tray_temporal_record), 8, "the record"},
-                              {frame_device, px * 24, 8, "the frame"}};
-    const int n_out = 5;
-    int n = 6;
+    Span spans[13];
+    int n = 0;
+    uint32_t nullable = 0;
+    spans[n++] = {out->colour, px * 24, 8, "out.colour"};
+    if (with_m2) spans[n++] = {out->m2, px * 24, 8, "out.m2"};
+    spans[n++] = {out->age, px * 4, 4, "out.age"};
+    spans[n++] = {out->index, px * 4, 4, "out.index"};
+    spans[n++] = {out->depth, px * 8, 8, "out.depth"};
+    if (with_m2) {
+        nullable |= 1u << n;
+        spans[n++] = {variance_device, px * 24, 8, "the variance"};
+    }
+    nullable |= 1u << n;
+    spans[n++] = {record_device, sizeof(tray_temporal_record), 8, "the record"};
+    const int n_out = n;
+    spans[n++] = {frame_device, px * 24, 8, "the frame"};
     if (history) {
         spans[n++] = {history->colour, px * 24, 8, "history.colour"};
+        if (with_m2) spans[n++] = {history->m2, px * 24, 8, "history.m2"};
         spans[n++] = {history->age, px * 4, 4, "history.age"};
         spans[n++] = {history->index, px * 4, 4, "history.index"};
         spans[n++] = {history->depth, px * 8, 8, "history.depth"};
     }
-    for (int i = 0; i < n; ++i)
-        if (!spans[i].p && i != 4) return fail(TRAY_ERR_INVALID_ARGUMENT, std::string("null buffer: ") + spans[i].name);
-    for (int i = 0; i < n; ++i)
-        if ((uintptr_t)spans[i].p & (spans[i].align - 1))
-            return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(spans[i].name) + " is not " +
-                                                       (spans[i].align == 8 ? "8" : "4") + "-byte aligned");
-    for (int i = 0; i < n_out; ++i)
-        for (int j = i + 1; j < n; ++j)
-            if (spans_overlap(spans[i], spans[j]))
-                return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(spans[i].name) + " overlaps " + spans[j].name);
+    int rc = check_nulls(spans, n, nullable);
+    if (!rc) rc = check_alignment(spans, n);
+    if (!rc) rc = check_overlaps(spans, n, n_out);
+    if (rc) return rc;
     KernelParams k;
     memset(&k, 0, sizeof(k));
     scene_params(sc, k);
@@ -1211,8 +1203,23 @@ int tray_temporal_step_async(tray_scene_t sc, const tray_camera* cam, const tray
     k.rows = out->height;
     TRAY_HIP(hipSetDevice(sc->device));
     TRAY_HIP(launch_temporal_step(k, wants_bvh(sc, tp->flags), sc->bvh_bound, prev, *tp, frame_device, history, *out,
-                                  record_device, static_cast<hipStream_t>(stream)));
+                                  variance_device, record_device, static_cast<hipStream_t>(stream)));
     return TRAY_OK;
+}
+
+static tray_temporal_var_state without_m2(const tray_temporal_state& s) {
+    return tray_temporal_var_state{s.colour, nullptr, s.age, s.index, s.depth, s.width, s.height};
+}
+
+int tray_temporal_step_async(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
+                             const tray_temporal_params* tp, const double* frame_device,
+                             const tray_temporal_state* history, const tray_temporal_state* out,
+                             tray_temporal_record* record_device, void* stream) {
+    tray_temporal_var_state h{}, o{};
+    if (history) h = without_m2(*history);
+    if (out) o = without_m2(*out);
+    return temporal_step(sc, cam, prev, tp, frame_device, history ? &h : nullptr, out ? &o : nullptr, false, nullptr,
+                         record_device, stream);
 }
 
 // ---- temporal reprojection with M2 (include/tray_temporal_variance.h) --------------
@@ -1222,68 +1229,7 @@ int tray_temporal_var_step_async(tray_scene_t sc, const tray_camera* cam, const 
                                  const tray_temporal_params* tp, const double* frame_device,
                                  const tray_temporal_var_state* history, const tray_temporal_var_state* out,
                                  double* variance_device, tray_temporal_record* record_device, void* stream) {
-    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
-    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
-    if (!tp) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params");
-    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null state (out)");
-    if ((history == nullptr) != (prev == nullptr))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "history and prev_camera must both be given or both be null");
-    if (out->width < 0 || out->height < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative width or height");
-    if (history && (history->width != out->width || history->height != out->height))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "history and out differ in width or height");
-    if (tp->max_history < 1 || tp->max_history > (1 << 30))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "max_history must be in 1 .. 2^30");
-    if (tp->flags & ~TRAY_FLAG_LINEAR_SCAN)
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "unknown flags (only TRAY_FLAG_LINEAR_SCAN applies)");
-    if (!(std::isfinite(tp->depth_tolerance) && tp->depth_tolerance >= 0.0))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "depth_tolerance must be finite and >= 0");
-    if (!(std::isfinite(tp->snap) && tp->snap >= 0.0 && tp->snap < 0.5))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "snap must be finite, >= 0 and < 0.5");
-    if (tp->reserved != 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "reserved must be 0");
-    const int64_t image = (int64_t)out->width * (int64_t)out->height;
-    if (image > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
-    if (image == 0) return TRAY_OK;
-    // The spans: outputs first (the first n_out; the last two of them nullable), then what is only read.
-    const size_t px = (size_t)image;
-    TemporalSpan spans[13] = {{out->colour, px * 24, 8, "out.colour"},
-                              {out->m2, px * 24, 8, "out.m2"},
-                              {out->age, px * 4, 4, "out.age"},
-                              {out->index, px * 4, 4, "out.index"},
-                              {out->depth, px * 8, 8, "out.depth"},
-                              {variance_device, px * 24, 8, "the variance"},
-                              {record_device, sizeof(tray_temporal_record), 8, "the record"},
-                              {frame_device, px * 24, 8, "the frame"}};
-    const int n_out = 7;
-    int n = 8;
-    if (history) {
-        spans[n++] = {history->colour, px * 24, 8, "history.colour"};
-        spans[n++] = {history->m2, px * 24, 8, "history.m2"};
-        spans[n++] = {history->age, px * 4, 4, "history.age"};
-        spans[n++] = {history->index, px * 4, 4, "history.index"};
-        spans[n++] = {history->depth, px * 8, 8, "history.depth"};
-    }
-    for (int i = 0; i < n; ++i)
-        if (!spans[i].p && i != 5 && i != 6)
-            return fail(TRAY_ERR_INVALID_ARGUMENT, std::string("null buffer: ") + spans[i].name);
-    for (int i = 0; i < n; ++i)
-        if ((uintptr_t)spans[i].p & (spans[i].align - 1))
-            return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(spans[i].name) + " is not " +
-                                                       (spans[i].align == 8 ? "8" : "4") + "-byte aligned");
-    for (int i = 0; i < n_out; ++i)
-        for (int j = i + 1; j < n; ++j)
-            if (spans_overlap(spans[i], spans[j]))
-                return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(spans[i].name) + " overlaps " + spans[j].name);
-    KernelParams k;
-    memset(&k, 0, sizeof(k));
-    scene_params(sc, k);
-    camera_params(cam, k);
-    k.width = out->width;
-    k.height = out->height;
-    k.rows = out->height;
-    TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_temporal_var_step(k, wants_bvh(sc, tp->flags), sc->bvh_bound, prev, *tp, frame_device, history,
-                                      *out, variance_device, record_device, static_cast<hipStream_t>(stream)));
-    return TRAY_OK;
+    return temporal_step(sc, cam, prev, tp, frame_device, history, out, true, variance_device, record_device, stream);
 }
 
 int tray_temporal_var_variance_async(const tray_temporal_var_state* state, const uint32_t* pixels_device,
@@ -1292,24 +1238,18 @@ int tray_temporal_var_variance_async(const tray_temporal_var_state* state, const
     if (state->width < 0 || state->height < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative width or height");
     if (pixels_device && n_pixels < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative n_pixels");
     const int64_t image = (int64_t)state->width * (int64_t)state->height;
-    if (image > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
-    if (pixels_device && n_pixels > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "n_pixels exceeds 2^31 - 1");
+    if (image > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
+    if (pixels_device && n_pixels > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "n_pixels exceeds 2^31 - 1");
     if (image == 0 || (pixels_device && n_pixels == 0)) return TRAY_OK;
     const size_t px = (size_t)image;
-    const TemporalSpan spans[4] = {{variance_device, px * 24, 8, "the variance"},
-                                   {state->m2, px * 24, 8, "m2"},
-                                   {state->age, px * 4, 4, "age"},
-                                   {pixels_device, pixels_device ? (size_t)n_pixels * 4 : 0, 4, "the pixel list"}};
-    for (int i = 0; i < 3; ++i)
-        if (!spans[i].p) return fail(TRAY_ERR_INVALID_ARGUMENT, std::string("null buffer: ") + spans[i].name);
-    for (int i = 0; i < 4; ++i)
-        if ((uintptr_t)spans[i].p & (spans[i].align - 1))
-            return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(spans[i].name) + " is not " +
-                                                       (spans[i].align == 8 ? "8" : "4") + "-byte aligned");
-    for (int j = 1; j < 4; ++j)
-        if (spans_overlap(spans[0], spans[j]))
-            return fail(TRAY_ERR_INVALID_ARGUMENT, std::string("the variance overlaps ") + spans[j].name);
-    const int rc = device_usable(device);
+    const Span spans[4] = {{variance_device, px * 24, 8, "the variance"},
+                           {state->m2, px * 24, 8, "m2"},
+                           {state->age, px * 4, 4, "age"},
+                           {pixels_device, pixels_device ? (size_t)n_pixels * 4 : 0, 4, "the pixel list"}};
+    int rc = check_nulls(spans, 4, 1u << 3);
+    if (!rc) rc = check_alignment(spans, 4);
+    if (!rc) rc = check_overlaps(spans, 4, 1);
+    if (!rc) rc = device_usable(device);
     if (rc) return rc;
     TRAY_HIP(hipSetDevice(device));
     TRAY_HIP(launch_temporal_variance(state->m2, state->age, (uint32_t)image, pixels_device,

@@ -15,7 +15,7 @@
 #include <string>
 
 #include "../../include/tray_adaptive.h"
-#include "tray_internal.hpp"
+#include "tray_check.hpp"
 #include "tray_query_device.hpp"
 #include "tray_stream.hpp"
 
@@ -444,37 +444,6 @@ __global__ __launch_bounds__(kWave) void adaptive_scan_kernel(const SelectArgs A
     if (lane == 0) A.record->n_active = carry;
 }
 
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
-bool misaligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) != 0; }
-
-struct Span {
-    const void* p;
-    size_t bytes;
-    const char* name;
-};
-
-// The first overlapping pair among `s` as an error, else TRAY_OK.
-int check_overlaps(const Span* s, int n) {
-    for (int i = 0; i < n; ++i)
-        for (int j = i + 1; j < n; ++j)
-            if (overlap(s[i].p, s[i].bytes, s[j].p, s[j].bytes))
-                return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(s[i].name) + " overlaps " + s[j].name);
-    return TRAY_OK;
-}
-
-int select_device(int32_t device) {
-    int n_devices = 0;
-    if (hipGetDeviceCount(&n_devices) != hipSuccess || n_devices <= 0) return fail(TRAY_ERR_NO_DEVICE, "no device");
-    if (device < 0 || device >= n_devices) return fail(TRAY_ERR_INVALID_ARGUMENT, "no such device");
-    const hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(TRAY_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    return TRAY_OK;
-}
-
 // The header's workspace formula for P > 0 pixels: the flag plane, then the block totals.
 size_t flag_plane_bytes(int64_t pixels) { return (size_t)((pixels + 7) / 8 * 8); }
 int64_t scan_blocks(int64_t pixels) { return (pixels + kScanPixels - 1) / kScanPixels; }
@@ -510,24 +479,22 @@ int tray_adaptive_fold_async(const tray_adaptive_state* st, const uint32_t* pixe
     if (n_pixels < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative n_pixels");
     if (n_passes < 1 || n_passes > 65535) return fail(TRAY_ERR_INVALID_ARGUMENT, "n_passes must be in 1..65535");
     const int64_t image = (int64_t)st->width * (int64_t)st->rows;
-    if (image > 0x7FFFFFFFll) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
-    if (n_pixels > 0x7FFFFFFFll) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one list");
+    if (image > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
+    if (n_pixels > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one list");
     if (image == 0 || n_pixels == 0) return TRAY_OK;
     if (!st->mean || !st->m2) return fail(TRAY_ERR_INVALID_ARGUMENT, "null mean or m2");
     if (!st->count) return fail(TRAY_ERR_INVALID_ARGUMENT, "null count");
     if (!pixels) return fail(TRAY_ERR_INVALID_ARGUMENT, "null pixels");
     if (!values) return fail(TRAY_ERR_INVALID_ARGUMENT, "null values");
-    if (misaligned(st->mean, 8) || misaligned(st->m2, 8) || misaligned(values, 8))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "a buffer is not 8-byte aligned");
-    if (misaligned(st->count, 4) || misaligned(pixels, 4))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "count or pixels is not 4-byte aligned");
     const size_t img = (size_t)image * 3 * sizeof(double);
-    const Span spans[] = {{st->mean, img, "mean"},
-                          {st->m2, img, "m2"},
-                          {st->count, (size_t)image * sizeof(int32_t), "count"},
-                          {pixels, (size_t)n_pixels * sizeof(uint32_t), "pixels"},
-                          {values, (size_t)n_pixels * (size_t)n_passes * 3 * sizeof(double), "values"}};
-    int rc = check_overlaps(spans, 5);
+    const Span spans[] = {{st->mean, img, 8, "mean"},
+                          {st->m2, img, 8, "m2"},
+                          {st->count, (size_t)image * sizeof(int32_t), 4, "count"},
+                          {pixels, (size_t)n_pixels * sizeof(uint32_t), 4, "pixels"},
+                          {values, (size_t)n_pixels * (size_t)n_passes * 3 * sizeof(double), 8, "values"}};
+    int rc = check_alignment(spans, 5);
+    if (rc) return rc;
+    rc = check_overlaps(spans, 5, 5);
     if (rc) return rc;
     rc = select_device(device);
     if (rc) return rc;
@@ -552,7 +519,7 @@ int tray_adaptive_workspace_bytes(int32_t width, int32_t rows, size_t* bytes) {
     if (!bytes) return fail(TRAY_ERR_INVALID_ARGUMENT, "null bytes");
     if (width < 0 || rows < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative width or rows");
     const int64_t image = (int64_t)width * (int64_t)rows;
-    if (image > 0x7FFFFFFFll) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
+    if (image > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
     *bytes = workspace_bytes(image);
     return TRAY_OK;
 }
@@ -574,27 +541,24 @@ int tray_adaptive_select_async(const tray_adaptive_state* st, const tray_adaptiv
     if (!pixels) return fail(TRAY_ERR_INVALID_ARGUMENT, "null pixels");
     if (!record) return fail(TRAY_ERR_INVALID_ARGUMENT, "null record");
     const int64_t image = (int64_t)st->width * (int64_t)st->rows;
-    if (image > 0x7FFFFFFFll) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
+    if (image > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
     if (image == 0) return TRAY_OK;
     if (!st->mean || !st->m2) return fail(TRAY_ERR_INVALID_ARGUMENT, "null mean or m2");
     if (!st->count) return fail(TRAY_ERR_INVALID_ARGUMENT, "null count");
     const size_t need = workspace_bytes(image);
     if (!workspace || workspace_size < need)
         return fail(TRAY_ERR_INVALID_ARGUMENT, "workspace is null or smaller than tray_adaptive_workspace_bytes");
-    if (misaligned(st->mean, 8) || misaligned(st->m2, 8) || misaligned(variance, 8) || misaligned(record, 8) ||
-        misaligned(workspace, 8))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "a buffer is not 8-byte aligned");
-    if (misaligned(st->count, 4) || misaligned(pixels, 4))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "count or pixels is not 4-byte aligned");
     const size_t img = (size_t)image * 3 * sizeof(double);
-    const Span spans[] = {{st->mean, img, "mean"},
-                          {st->m2, img, "m2"},
-                          {st->count, (size_t)image * sizeof(int32_t), "count"},
-                          {variance, img, "variance"},
-                          {pixels, (size_t)image * sizeof(uint32_t), "pixels"},
-                          {record, sizeof(tray_adaptive_record), "the record"},
-                          {workspace, need, "the workspace"}};
-    int rc = check_overlaps(spans, 7);
+    const Span spans[] = {{st->mean, img, 8, "mean"},
+                          {st->m2, img, 8, "m2"},
+                          {st->count, (size_t)image * sizeof(int32_t), 4, "count"},
+                          {variance, img, 8, "variance"},
+                          {pixels, (size_t)image * sizeof(uint32_t), 4, "pixels"},
+                          {record, sizeof(tray_adaptive_record), 8, "the record"},
+                          {workspace, need, 8, "the workspace"}};
+    int rc = check_alignment(spans, 7);
+    if (rc) return rc;
+    rc = check_overlaps(spans, 7, 7);
     if (rc) return rc;
     rc = select_device(device);
     if (rc) return rc;

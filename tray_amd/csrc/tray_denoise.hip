@@ -32,7 +32,7 @@
 
 #include "../../include/tray_denoise.h"
 #include "../../include/tray_progressive.h"
-#include "tray_internal.hpp"
+#include "tray_check.hpp"
 
 namespace tray {
 namespace {
@@ -346,15 +346,10 @@ int validate(const tray_denoise_params* p, int64_t* pixels, size_t* workspace) {
         if (!(std::isfinite(sigmas[i]) && sigmas[i] > 0.0))
             return fail(TRAY_ERR_INVALID_ARGUMENT, std::string(names[i]) + " must be finite and > 0");
     *pixels = (int64_t)p->width * (int64_t)p->rows;
-    if (*pixels > 0x7FFFFFFFll) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one denoise call");
+    if (*pixels > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one denoise call");
     const size_t images = p->iterations >= 3 ? 2 : (size_t)(p->iterations - 1);
     *workspace = images * (size_t)*pixels * 3 * sizeof(double);
     return TRAY_OK;
-}
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 #ifndef TRAY_DENOISE_GLOBAL_TAPS
@@ -411,17 +406,20 @@ int tray_denoise_async(const double* colour, const tray_denoise_guides* guides, 
     if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null out");
     int64_t pixels = 0;
     size_t need = 0;
-    const int rc = validate(p, &pixels, &need);
+    int rc = validate(p, &pixels, &need);
     if (rc) return rc;
     if ((p->flags & TRAY_DENOISE_DEMODULATE) && !guides->albedo)
         return fail(TRAY_ERR_INVALID_ARGUMENT, "TRAY_DENOISE_DEMODULATE needs the albedo guide");
     if (need && (!workspace || workspace_bytes < need))
         return fail(TRAY_ERR_INVALID_ARGUMENT, "workspace smaller than tray_denoise_workspace_bytes");
     const size_t image_bytes = (size_t)pixels * 3 * sizeof(double);
-    if (overlap(out, image_bytes, colour, image_bytes))
+    const Span spans[] = {{out, image_bytes, 0, "out"},
+                          {colour, image_bytes, 0, "colour"},
+                          {workspace, need, 0, "the workspace"}};
+    if (spans_overlap(spans[0], spans[1]))
         return fail(TRAY_ERR_INVALID_ARGUMENT, "out overlaps colour: the filter does not run in place");
-    if (need && overlap(out, image_bytes, workspace, need))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "out overlaps the workspace");
+    rc = check_overlaps(spans, 3, 1);
+    if (rc) return rc;
     if (pixels == 0) return TRAY_OK;
 
     const bool modulate = (p->flags & TRAY_DENOISE_DEMODULATE) != 0;
@@ -440,11 +438,8 @@ int tray_denoise_async(const double* colour, const tray_denoise_guides* guides, 
             return fail(TRAY_ERR_TOO_LARGE, "a level of this image needs more than 2^24 - 1 workgroups");
     }
 
-    int n_devices = 0;
-    if (hipGetDeviceCount(&n_devices) != hipSuccess || n_devices <= 0) return fail(TRAY_ERR_NO_DEVICE, "no device");
-    if (device < 0 || device >= n_devices) return fail(TRAY_ERR_INVALID_ARGUMENT, "no such device");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(TRAY_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    rc = select_device(device);
+    if (rc) return rc;
     double sigma_c = p->sigma_color;
     const double* in = colour;
     for (int i = 0; i < p->iterations; ++i) {
@@ -455,7 +450,7 @@ int tray_denoise_async(const double* colour, const tray_denoise_guides* guides, 
         L.remodulate = modulate && last ? guides->albedo : nullptr;
         L.s = 1 << i;
         L.q_c = 1.0 / (sigma_c * sigma_c);
-        e = launch_level(L, static_cast<hipStream_t>(stream));
+        const hipError_t e = launch_level(L, static_cast<hipStream_t>(stream));
         if (e != hipSuccess) return fail(TRAY_ERR_DEVICE, std::string("denoise level: ") + hipGetErrorString(e));
         in = L.out;
         sigma_c = sigma_c * 0.5;
@@ -494,23 +489,22 @@ int tray_denoise_variance_async(const double* colour, const double* variance, co
     if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null out");
     int64_t pixels = 0;
     size_t need = 0;
-    const int rc = validate_variance(p, &pixels, &need);
+    int rc = validate_variance(p, &pixels, &need);
     if (rc) return rc;
     if ((p->flags & TRAY_DENOISE_DEMODULATE) && !guides->albedo)
         return fail(TRAY_ERR_INVALID_ARGUMENT, "TRAY_DENOISE_DEMODULATE needs the albedo guide");
     if (need && (!workspace || workspace_bytes < need))
         return fail(TRAY_ERR_INVALID_ARGUMENT, "workspace smaller than tray_denoise_variance_workspace_bytes");
     const size_t image_bytes = (size_t)pixels * 3 * sizeof(double), plane_bytes = (size_t)pixels * sizeof(double);
-    if (overlap(out, image_bytes, colour, image_bytes))
+    const Span spans[] = {{out, image_bytes, 0, "out"},
+                          {variance_out, plane_bytes, 0, "variance_out"},
+                          {colour, image_bytes, 0, "colour"},
+                          {variance, image_bytes, 0, "variance"},
+                          {workspace, need, 0, "the workspace"}};
+    if (spans_overlap(spans[0], spans[2]))
         return fail(TRAY_ERR_INVALID_ARGUMENT, "out overlaps colour: the filter does not run in place");
-    if (overlap(out, image_bytes, variance, image_bytes)) return fail(TRAY_ERR_INVALID_ARGUMENT, "out overlaps variance");
-    if (need && overlap(out, image_bytes, workspace, need))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "out overlaps the workspace");
-    if (variance_out && (overlap(variance_out, plane_bytes, colour, image_bytes) ||
-                         overlap(variance_out, plane_bytes, variance, image_bytes) ||
-                         overlap(variance_out, plane_bytes, out, image_bytes) ||
-                         (need && overlap(variance_out, plane_bytes, workspace, need))))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "variance_out overlaps another buffer");
+    rc = check_overlaps(spans, 5, 2);
+    if (rc) return rc;
     if (pixels == 0) return TRAY_OK;
 
     const bool modulate = (p->flags & TRAY_DENOISE_DEMODULATE) != 0;
@@ -533,11 +527,8 @@ int tray_denoise_variance_async(const double* colour, const double* variance, co
             return fail(TRAY_ERR_TOO_LARGE, "a level of this image needs more than 2^24 - 1 workgroups");
     }
 
-    int n_devices = 0;
-    if (hipGetDeviceCount(&n_devices) != hipSuccess || n_devices <= 0) return fail(TRAY_ERR_NO_DEVICE, "no device");
-    if (device < 0 || device >= n_devices) return fail(TRAY_ERR_INVALID_ARGUMENT, "no such device");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(TRAY_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    rc = select_device(device);
+    if (rc) return rc;
     VarianceLevel V;
     V.S = p->sigma_variance * p->sigma_variance;
     V.epsilon = p->epsilon;
@@ -553,7 +544,7 @@ int tray_denoise_variance_async(const double* colour, const double* variance, co
         V.variance = i == 0 ? variance : nullptr;
         V.plane_in = plane_in;
         V.plane_out = last ? variance_out : planes[i & 1];
-        e = launch_variance_level(L, V, static_cast<hipStream_t>(stream));
+        const hipError_t e = launch_variance_level(L, V, static_cast<hipStream_t>(stream));
         if (e != hipSuccess)
             return fail(TRAY_ERR_DEVICE, std::string("variance-guided denoise level: ") + hipGetErrorString(e));
         in = L.out;

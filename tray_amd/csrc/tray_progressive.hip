@@ -33,7 +33,7 @@
 #include <string>
 
 #include "../../include/tray_progressive.h"
-#include "tray_internal.hpp"
+#include "tray_check.hpp"
 #include "tray_stream.hpp"
 
 namespace tray {
@@ -177,13 +177,6 @@ __global__ __launch_bounds__(kThreads) void accum_fold_kernel(const FoldArgs A) 
     }
 }
 
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
-bool misaligned(const void* p) { return ((uintptr_t)p & 7) != 0; }
-
 int fold(tray_accum* acc, const double* frames, int32_t n_frames, bool with_metric,
          const tray_accum_metric_params* mp, double* variance, tray_accum_metric* metric, int32_t device,
          void* stream) {
@@ -192,7 +185,7 @@ int fold(tray_accum* acc, const double* frames, int32_t n_frames, bool with_metr
     if (acc->count < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative count");
     if (acc->reserved != 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "reserved must be 0");
     if (n_frames < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative n_frames");
-    if ((int64_t)acc->count + n_frames > 0x7FFFFFFFll)
+    if ((int64_t)acc->count + n_frames > INT32_MAX)
         return fail(TRAY_ERR_INVALID_ARGUMENT, "count + n_frames overflows int32");
     if (with_metric) {
         if (!mp) return fail(TRAY_ERR_INVALID_ARGUMENT, "null metric params");
@@ -202,36 +195,27 @@ int fold(tray_accum* acc, const double* frames, int32_t n_frames, bool with_metr
             return fail(TRAY_ERR_INVALID_ARGUMENT, "floor must be finite and > 0");
     }
     const int64_t pixels = (int64_t)acc->width * (int64_t)acc->rows;
-    if (pixels > 0x7FFFFFFFll) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one accumulator");
+    if (pixels > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one accumulator");
     if (pixels == 0) return TRAY_OK;
     if (!with_metric && n_frames == 0) return TRAY_OK;
     if (!acc->mean || !acc->m2) return fail(TRAY_ERR_INVALID_ARGUMENT, "null mean or m2");
     if (n_frames > 0 && !frames) return fail(TRAY_ERR_INVALID_ARGUMENT, "null frames");
-    if (misaligned(acc->mean) || misaligned(acc->m2) || misaligned(frames) || misaligned(variance) ||
-        misaligned(metric))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "a buffer is not 8-byte aligned");
+    const size_t image = (size_t)pixels * 3 * sizeof(double);
+    const Span spans[] = {{metric, sizeof(tray_accum_metric), 8, "the metric record"},
+                          {variance, image, 8, "variance"},
+                          {acc->mean, image, 8, "mean"},
+                          {acc->m2, image, 8, "m2"},
+                          {frames, image * (size_t)n_frames, 8, "the frames"}};
+    int rc = check_alignment(spans, 5);
+    if (rc) return rc;
     if (with_metric && acc->count + n_frames == 0)
         return fail(TRAY_ERR_INVALID_ARGUMENT, "no frames folded: nothing to evaluate");
-    const size_t image = (size_t)pixels * 3 * sizeof(double), stack = image * (size_t)n_frames;
-    if (overlap(acc->mean, image, acc->m2, image)) return fail(TRAY_ERR_INVALID_ARGUMENT, "mean overlaps m2");
-    if (overlap(acc->mean, image, frames, stack) || overlap(acc->m2, image, frames, stack))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "the state overlaps the frames");
-    if (overlap(variance, image, acc->mean, image) || overlap(variance, image, acc->m2, image) ||
-        overlap(variance, image, frames, stack))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "variance overlaps the state or the frames");
-    if (overlap(metric, sizeof(tray_accum_metric), acc->mean, image) ||
-        overlap(metric, sizeof(tray_accum_metric), acc->m2, image) ||
-        overlap(metric, sizeof(tray_accum_metric), frames, stack) ||
-        overlap(metric, sizeof(tray_accum_metric), variance, image))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "the metric record overlaps another buffer");
+    rc = check_overlaps(spans, 5, 4);
+    if (rc) return rc;
     const bool evaluate = with_metric && (variance || metric);
     if (!evaluate && n_frames == 0) return TRAY_OK;
-
-    int n_devices = 0;
-    if (hipGetDeviceCount(&n_devices) != hipSuccess || n_devices <= 0) return fail(TRAY_ERR_NO_DEVICE, "no device");
-    if (device < 0 || device >= n_devices) return fail(TRAY_ERR_INVALID_ARGUMENT, "no such device");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(TRAY_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    rc = select_device(device);
+    if (rc) return rc;
 
     FoldArgs A;
     A.mean = acc->mean;
@@ -250,6 +234,7 @@ int fold(tray_accum* acc, const double* frames, int32_t n_frames, bool with_metr
     A.floor = with_metric ? mp->floor : 1.0;
     const uint32_t grid = (uint32_t)((int64_t)A.chunks < kMaxGrid ? (int64_t)A.chunks : kMaxGrid);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipSuccess;
     if (A.metric) {
         e = hipMemsetAsync(metric, 0, sizeof(tray_accum_metric), s);
         if (e != hipSuccess) return fail(TRAY_ERR_DEVICE, std::string("hipMemsetAsync: ") + hipGetErrorString(e));

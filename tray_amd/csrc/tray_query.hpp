@@ -69,21 +69,16 @@ hipError_t launch_render_pixels(KernelParams p, bool use_bvh, double bound, cons
                                 const int32_t* pass_plane, uint32_t n_passes, double* out, uint32_t* segments,
                                 hipStream_t stream);
 
-// include/tray_temporal.h section 2 (tray_temporal.hip).
+// include/tray_temporal.h and tray_temporal_variance.h, section 2 of each (tray_temporal.hip).
 // One reprojection step over the out.width x out.height frame: p's scene and camera fields and
 // p.width, p.height. `history` and `prev` both null: the first frame. `record` nullable (zeroed
-// on `stream` ahead of the launch). use_bvh and bound as for launch_scene_hit.
+// on `stream` ahead of the launch). use_bvh and bound as for launch_scene_hit. out.m2 null: the
+// plain step, with history's m2 and `variance` null too; else the step with the M2 planes and
+// the (nullable) variance of the mean.
 hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
                                 const tray_temporal_params& tp, const double* frame,
-                                const tray_temporal_state* history, const tray_temporal_state& out,
-                                tray_temporal_record* record, hipStream_t stream);
-
-// include/tray_temporal_variance.h section 2 (tray_temporal.hip): launch_temporal_step with the
-// M2 planes and the (nullable) variance of the mean.
-hipError_t launch_temporal_var_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
-                                    const tray_temporal_params& tp, const double* frame,
-                                    const tray_temporal_var_state* history, const tray_temporal_var_state& out,
-                                    double* variance, tray_temporal_record* record, hipStream_t stream);
+                                const tray_temporal_var_state* history, const tray_temporal_var_state& out,
+                                double* variance, tray_temporal_record* record, hipStream_t stream);
 
 // include/tray_temporal_variance.h section 3 (tray_temporal.hip): the variance of the mean of the
 // n_pixels listed pixels (entries >= image_pixels skipped), or of every pixel when `pixels` is null.

@@ -217,11 +217,15 @@ __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaun
     }
 }
 
-// The launch of either instance: m2_out null is the plain step.
-static hipError_t launch_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
-                              const tray_temporal_params& tp, const double* frame, const tray_temporal_state* history,
-                              const double* history_m2, const tray_temporal_state& out, double* out_m2,
-                              double* variance, tray_temporal_record* record, hipStream_t stream) {
+static tray_temporal_state plain_state(const tray_temporal_var_state& s) {
+    return tray_temporal_state{s.colour, s.age, s.index, s.depth, s.width, s.height};
+}
+
+// The launch of either instance: out.m2 null is the plain step.
+hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
+                                const tray_temporal_params& tp, const double* frame,
+                                const tray_temporal_var_state* history, const tray_temporal_var_state& out,
+                                double* variance, tray_temporal_record* record, hipStream_t stream) {
     if (out.width <= 0 || out.height <= 0) return hipSuccess;
     size_t lds = 0;
     QueryArgs q = query_args(p, use_bvh, bound, nullptr, 0, lds);
@@ -231,16 +235,16 @@ static hipError_t launch_step(KernelParams p, bool use_bvh, double bound, const 
     }
     TemporalArgs a{};
     a.frame = frame;
-    a.out = out;
+    a.out = plain_state(out);
     a.record = record;
     a.depth_tolerance = tp.depth_tolerance;
     a.snap = tp.snap;
     a.max_history = tp.max_history;
-    a.out_m2 = out_m2;
+    a.out_m2 = out.m2;
     a.variance = variance;
     if (history && prev && tp.max_history > 1) {  // max_history 1: the frame itself (the header, section 3)
-        a.history = *history;
-        a.history_m2 = history_m2;
+        a.history = plain_state(*history);
+        a.history_m2 = history->m2;
         PrevCamera& P = a.prev;
         for (int c = 0; c < 3; ++c) {
             P.position[c] = prev->position[c];
@@ -258,34 +262,13 @@ static hipError_t launch_step(KernelParams p, bool use_bvh, double bound, const 
     hipError_t e = hipSuccess;
     if (record) e = hipMemsetAsync(record, 0, sizeof(*record), stream);
     if (e != hipSuccess) return e;
-    if (out_m2)
+    if (out.m2)
         hipLaunchKernelGGL(temporal_step_kernel<true>, dim3(a.tiles_x * tiles_y), dim3(kQueryBlock), lds, stream,
                            TemporalLaunch{p, q, a});
     else
         hipLaunchKernelGGL(temporal_step_kernel<false>, dim3(a.tiles_x * tiles_y), dim3(kQueryBlock), lds, stream,
                            TemporalLaunch{p, q, a});
     return hipGetLastError();
-}
-
-hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
-                                const tray_temporal_params& tp, const double* frame,
-                                const tray_temporal_state* history, const tray_temporal_state& out,
-                                tray_temporal_record* record, hipStream_t stream) {
-    return launch_step(p, use_bvh, bound, prev, tp, frame, history, nullptr, out, nullptr, nullptr, record, stream);
-}
-
-static tray_temporal_state plain_state(const tray_temporal_var_state& s) {
-    return tray_temporal_state{s.colour, s.age, s.index, s.depth, s.width, s.height};
-}
-
-hipError_t launch_temporal_var_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
-                                    const tray_temporal_params& tp, const double* frame,
-                                    const tray_temporal_var_state* history, const tray_temporal_var_state& out,
-                                    double* variance, tray_temporal_record* record, hipStream_t stream) {
-    tray_temporal_state h{};
-    if (history) h = plain_state(*history);
-    return launch_step(p, use_bvh, bound, prev, tp, frame, history ? &h : nullptr, history ? history->m2 : nullptr,
-                       plain_state(out), out.m2, variance, record, stream);
 }
 
 // ---- include/tray_temporal_variance.h section 3: the variance of the mean from (m2, age) ----

@@ -358,6 +358,17 @@ REFILL_DEFAULT = 3  # the CLI's -refill without a number (tools/temporal_varianc
 
 # --------------------------------------------------------------------- tracer
 _CAMERA_FIELDS = ("Position", "LookAt", "Up", "VerticalFoV", "FocalLength", "FocusDistance", "Aperture")
+_GUIDES = (("albedo", 3), ("normal", 3), ("depth", 1))  # the filters' guides: name, channels
+
+
+def _guide_ptrs(aov: dict) -> list:
+    """The device pointers of the guides in `aov`, in the C calls' order; None where it has none."""
+    return [aov[name].data_ptr() if aov.get(name) is not None else None for name, _ in _GUIDES]
+
+
+def _given(**kw) -> dict:
+    """The arguments that are not None: the library's defaults stand for the others."""
+    return {name: value for name, value in kw.items() if value is not None}
 
 
 class Tracer:  # ray/tracer.go:25-36
@@ -416,9 +427,64 @@ class Tracer:  # ray/tracer.go:25-36
         # Seed 0 means "randomized each time" (tracer.go:33).
         return self.Seed if self.Seed else int.from_bytes(os.urandom(8), "little") or 1
 
+    # ---- what the device-side methods below share: a new one is built from these ----
+    def _target(self):
+        """Where those methods run: torch, the device's index, its torch.device and the current
+        stream there (which initializes the device: call it once the arguments are checked)."""
+        import torch
+
+        device = int(self.Devices[0] if self.Devices else self.Device)
+        where = torch.device(f"cuda:{device}")
+        return torch, device, where, torch.cuda.current_stream(where).cuda_stream
+
+    def _params(self, seed: int, pass_: int = 0, flags: int = 0, y0: int = 0, y1: int | None = None):
+        """The tracer's tray_params for progressive pass `pass_` of rows [y0, y1), the frame's by default."""
+        return _lib.make_params(self.width, self.height, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, seed,
+                                y0, y1, flags=flags, pass_=pass_)
+
+    def _guide_buffers(self, torch, where) -> dict:
+        """Device buffers for the filters' three guides over the frame, for tray_render_aov_async."""
+        return {name: torch.empty((self.height, self.width, 3)[: 3 if ch > 1 else 2], dtype=torch.float64,
+                                  device=where) for name, ch in _GUIDES}
+
+    def _upload_guides(self, guides: dict, rows: int) -> dict:
+        """A caller's host guides (as RenderAOV returns; a missing or None entry drops its term)
+        as device tensors. Each must cover `rows` rows of the image's width: else ValueError,
+        before any device work."""
+        host = {}
+        for name, ch in _GUIDES:
+            g = guides.get(name)
+            if g is None:
+                continue
+            g = np.ascontiguousarray(g, dtype=np.float64)
+            if g.shape != (rows, self.width) + ((3,) if ch == 3 else ()):
+                raise ValueError(f"{name} must cover the frame's {rows} rows of {self.width} pixels; got {g.shape}")
+            host[name] = g
+        if rows * self.width == 0:
+            return {}
+        torch, _, where, _ = self._target()
+        return {name: torch.from_numpy(g).to(where) for name, g in host.items()}
+
+    def _frame_guides(self, torch, dev, guides: dict | None, where, stream) -> dict:
+        """The device guides for a filter over the whole frame: the caller's `guides` or, when
+        None, the feature buffers of pass 0 of `seed` (tray_render_aov_async on `stream`)."""
+        if guides is not None:
+            return self._upload_guides(guides, self.height)
+        aov = self._guide_buffers(torch, where)
+        dev.render_aov_async(self.Camera._state, self._params(self.seed), *_guide_ptrs(aov), stream=stream)
+        return aov
+
+    def _show(self, torch, shown, device: int, stream) -> np.ndarray:
+        """ColorF.ToSRGBA of the device frame `shown` (tray_linear_to_srgba_async) and the readback:
+        `linear` holds `shown` and imageData, which is returned, its (H, W, 4) uint8 RGBA."""
+        rgba = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device=shown.device)
+        _lib.linear_to_srgba_async(shown.data_ptr(), self.height * self.width, rgba.data_ptr(), device, stream)
+        self.linear[:] = shown.cpu().numpy()
+        self.imageData[:] = rgba.cpu().numpy()
+        return self.imageData
+
     def _render_rows(self, y0: int, y1: int, scene: Scene) -> None:
-        params = _lib.make_params(self.width, self.height, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius,
-                                  self._seed(), y0, y1)
+        params = self._params(self._seed(), y0=y0, y1=y1)
         progress = None
         if self.ProgressFunc is not None:  # per row, while the device renders (tracer.go:126-128)
             def progress(rows):
@@ -443,20 +509,16 @@ class Tracer:  # ray/tracer.go:25-36
         _lib.RAY_DTYPE array of (yEnd - yStart) x width x NumRaysPerPixel rays (row,
         column, sample order), and their (pixel, sample word) pairs as an (n, 2)
         uint32 array for Scene.RayColor. Set Seed for rays that repeat."""
-        import torch
-
         if self.Camera._state is None:
             raise _lib.TrayError(_lib.TRAY_ERR_INVALID_ARGUMENT, "Camera.Initialize must be called first")
-        device = self.Devices[0] if self.Devices else self.Device
         params = _lib.make_params(self.width, self.height, max(self.MaxDepth, 1), max(self.NumRaysPerPixel, 1),
                                   self.RayRadius if self.RayRadius > 0 else 0.5, self._seed(), yStart, yEnd,
                                   pass_=pass_)
         n = _lib.camera_rays_count(params)
-        where = torch.device(f"cuda:{int(device)}")
+        torch, device, where, stream = self._target()
         rays = torch.empty((n, 6), dtype=torch.float64, device=where)
         ids = torch.empty((n, 2), dtype=torch.int32, device=where)
-        _lib.camera_rays_async(self.Camera._state, params, rays.data_ptr(), ids.data_ptr(), device,
-                               torch.cuda.current_stream(where).cuda_stream)
+        _lib.camera_rays_async(self.Camera._state, params, rays.data_ptr(), ids.data_ptr(), device, stream)
         return rays.cpu().numpy().reshape(-1).view(_lib.RAY_DTYPE), ids.cpu().numpy().view(np.uint32)
 
     def Render(self, scene: Scene | None) -> np.ndarray:  # ray/tracer.go:48-118
@@ -471,22 +533,18 @@ class Tracer:  # ray/tracer.go:25-36
         and normal (rows, W, 3) float64, depth and coverage (rows, W) float64, index
         (rows, W) int32 (-1: sample 0 misses). One fused launch over the frame's own camera
         rays of pass `pass_`; no Go counterpart. Set Seed for buffers that match a render."""
-        import torch
-
         scene = self._apply_defaults(scene)
         self.Camera.Initialize(self.width, self.height)
-        device = self.Devices[0] if self.Devices else self.Device
-        params = _lib.make_params(self.width, self.height, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius,
-                                  self._seed(), yStart, self.height if yEnd is None else yEnd, pass_=pass_)
+        params = self._params(self._seed(), pass_, y0=yStart, y1=yEnd)
         rows = _lib.params_rows(params)
-        where = torch.device(f"cuda:{int(device)}")
+        torch, device, where, stream = self._target()
         bufs = {name: torch.empty((rows, self.width, ch)[: 3 if ch > 1 else 2],
                                   dtype=torch.float64 if dt is np.float64 else torch.int32, device=where)
                 for name, ch, dt in _lib.AOV_BUFFERS}
         if rows > 0:  # an empty row set has no buffers to point at
             scene._device_scene(device).render_aov_async(
                 self.Camera._state, params, *(bufs[name].data_ptr() for name, _, _ in _lib.AOV_BUFFERS),
-                stream=torch.cuda.current_stream(where).cuda_stream)
+                stream=stream)
         return {name: t.cpu().numpy() for name, t in bufs.items()}
 
     def _denoise_device(self, torch, colour, aov: dict, overrides: dict):
@@ -495,15 +553,27 @@ class Tracer:  # ray/tracer.go:25-36
         (rows, W, 3) float64 tensor, enqueued on the current stream."""
         rows, width = int(colour.shape[0]), int(colour.shape[1])
         params = _lib.denoise_params(width, rows, **overrides)
-        guides = {name: aov.get(name) for name in ("albedo", "normal", "depth")}
         nbytes = _lib.denoise_workspace_bytes(params)
         out = torch.empty_like(colour)
         work = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=colour.device)
         _lib.denoise_async(colour.data_ptr(), params, out.data_ptr(), work.data_ptr() if nbytes else None, nbytes,
-                           *(g.data_ptr() if g is not None else None for g in guides.values()),
-                           device=colour.device.index or 0,
+                           *_guide_ptrs(aov), device=colour.device.index or 0,
                            stream=torch.cuda.current_stream(colour.device).cuda_stream)
         # `work` may be freed here: torch's allocator reuses it only for work on this same stream
+        return out
+
+    def _denoise_variance_device(self, torch, colour, variance, aov: dict, overrides: dict):
+        """tray_denoise_variance_async on device tensors, as _denoise_device: `variance` is the
+        (rows, W, 3) variance of the mean `colour`, overrides fields of tray_denoise_variance_params."""
+        rows, width = int(colour.shape[0]), int(colour.shape[1])
+        params = _lib.denoise_variance_params(width, rows, **overrides)
+        nbytes = _lib.denoise_variance_workspace_bytes(params)
+        out = torch.empty_like(colour)
+        work = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=colour.device)
+        _lib.denoise_variance_async(colour.data_ptr(), variance.data_ptr(), params, out.data_ptr(),
+                                    work.data_ptr() if nbytes else None, nbytes, *_guide_ptrs(aov),
+                                    device=colour.device.index or 0,
+                                    stream=torch.cuda.current_stream(colour.device).cuda_stream)
         return out
 
     def Denoise(self, frame, aov: dict, yStart: int = 0, yEnd: int | None = None, tile_rows: int = 0,
@@ -518,8 +588,6 @@ class Tracer:  # ray/tracer.go:25-36
         filter needs spatially contiguous rows, so [yStart, yEnd) must be a row range of the image
         with exactly the frame's number of rows (else ValueError), and any tile_rows > 0, an
         interleaved row set, raises ValueError."""
-        import torch
-
         yEnd = self.height if yEnd is None else yEnd
         if tile_rows > 0:
             raise ValueError("Denoise needs spatially contiguous rows: interleaved row sets (tile_rows > 0) are not")
@@ -527,22 +595,12 @@ class Tracer:  # ray/tracer.go:25-36
         if not 0 <= yStart <= yEnd <= self.height or frame.shape != (yEnd - yStart, self.width, 3):
             raise ValueError(f"frame must hold rows [{yStart}, {yEnd}) of the {self.width}-wide image as "
                              f"(rows, W, 3); got {frame.shape}")
-        host = {}
-        for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1)):
-            g = aov.get(name)
-            if g is None:
-                continue
-            g = np.ascontiguousarray(g, dtype=np.float64)
-            if g.shape != frame.shape[:2] + ((3,) if ch == 3 else ()):
-                raise ValueError(f"{name} must cover the frame's rows; got {g.shape}")
-            host[name] = g
-        where = torch.device(f"cuda:{int(self.Devices[0] if self.Devices else self.Device)}")
+        guides = self._upload_guides(aov, frame.shape[0])
         if frame.size == 0:
             _lib.denoise_params(self.width, 0, **overrides)  # still refuses unknown fields
             return frame.copy()
-        out = self._denoise_device(torch, torch.from_numpy(frame).to(where),
-                                   {n: torch.from_numpy(g).to(where) for n, g in host.items()}, overrides)
-        return out.cpu().numpy()
+        torch, _, where, _ = self._target()
+        return self._denoise_device(torch, torch.from_numpy(frame).to(where), guides, overrides).cpu().numpy()
 
     def RenderDenoised(self, scene: Scene | None, **overrides) -> np.ndarray:
         """Render(scene) at the tracer's few rays per pixel, made presentable: a linear FP64
@@ -551,29 +609,18 @@ class Tracer:  # ray/tracer.go:25-36
         (tray_linear_to_srgba_async), all enqueued on one stream with no host round trip in
         between. Returns (H, W, 4) uint8 RGBA like Render and keeps it in imageData; `linear`
         holds the denoised FP64 frame. overrides as for Denoise."""
-        import torch
-
         scene = self._apply_defaults(scene)
         self.Camera.Initialize(self.width, self.height)
-        device = int(self.Devices[0] if self.Devices else self.Device)
-        where = torch.device(f"cuda:{device}")
-        params = _lib.make_params(self.width, self.height, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius,
-                                  self._seed(), 0, self.height)
-        stream = torch.cuda.current_stream(where).cuda_stream
+        params = self._params(self._seed())
+        if self.height * self.width == 0:
+            return self.imageData
+        torch, device, where, stream = self._target()
         dev = scene._device_scene(device)
         colour = torch.empty((self.height, self.width, 3), dtype=torch.float64, device=where)
-        aov = {name: torch.empty((self.height, self.width, 3)[: 3 if ch > 1 else 2], dtype=torch.float64, device=where)
-               for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1))}
-        rgba = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device=where)
-        if self.height * self.width > 0:
-            dev.render_async(self.Camera._state, params, colour.data_ptr(), None, stream)
-            dev.render_aov_async(self.Camera._state, params, aov["albedo"].data_ptr(), aov["normal"].data_ptr(),
-                                 aov["depth"].data_ptr(), stream=stream)
-            out = self._denoise_device(torch, colour, aov, overrides)
-            _lib.linear_to_srgba_async(out.data_ptr(), self.height * self.width, rgba.data_ptr(), device, stream)
-            self.linear[:] = out.cpu().numpy()
-        self.imageData[:] = rgba.cpu().numpy()
-        return self.imageData
+        aov = self._guide_buffers(torch, where)
+        dev.render_async(self.Camera._state, params, colour.data_ptr(), None, stream)
+        dev.render_aov_async(self.Camera._state, params, *_guide_ptrs(aov), stream=stream)
+        return self._show(torch, self._denoise_device(torch, colour, aov, overrides), device, stream)
 
     def Accumulate(self, frames, tolerance: float | None = None, floor: float | None = None):
         """The running mean of a stack of linear frames, (k, rows, W, 3) float64 (for instance k
@@ -582,25 +629,21 @@ class Tracer:  # ray/tracer.go:25-36
         on the device in one launch. The variance is +inf for k < 2. `unconverged` and
         `max_ratio` receive the convergence record for `tolerance` and `floor` (the library's
         defaults when None). Any rows of the image's width do. No Go counterpart."""
-        import torch
-
         frames = np.ascontiguousarray(frames, dtype=np.float64)
         if frames.ndim != 4 or frames.shape[2:] != (self.width, 3) or frames.shape[0] < 1:
             raise ValueError(f"frames must be (k, rows, {self.width}, 3) with k >= 1; got {frames.shape}")
         k, rows = frames.shape[:2]
-        overrides = {n: v for n, v in (("tolerance", tolerance), ("floor", floor)) if v is not None}
-        mp = _lib.accum_metric_params(**overrides)
+        mp = _lib.accum_metric_params(**_given(tolerance=tolerance, floor=floor))
         if rows * self.width == 0:
             self.unconverged, self.max_ratio = 0, 0.0
             return frames[0].copy(), frames[0].copy()
-        device = int(self.Devices[0] if self.Devices else self.Device)
-        where = torch.device(f"cuda:{device}")
+        torch, device, where, stream = self._target()
         stack = torch.from_numpy(frames).to(where)
         mean, m2, variance = (torch.empty((rows, self.width, 3), dtype=torch.float64, device=where) for _ in range(3))
         record = torch.empty((2,), dtype=torch.float64, device=where)
         acc = _lib.Accum(mean.data_ptr(), m2.data_ptr(), self.width, rows, 0, 0)
         _lib.accum_fold_metric_async(acc, stack.data_ptr(), k, mp, variance.data_ptr(), record.data_ptr(), device,
-                                     torch.cuda.current_stream(where).cuda_stream)
+                                     stream)
         rec = record.cpu().numpy().view(_lib.ACCUM_METRIC_DTYPE)[0]
         self.unconverged, self.max_ratio = int(rec["unconverged"]), float(rec["max_ratio"])
         return mean.cpu().numpy(), variance.cpu().numpy()
@@ -625,54 +668,31 @@ class Tracer:  # ray/tracer.go:25-36
         (tray_linear_to_srgba_async) like Render and keeps it in imageData; `linear` holds the FP64
         frame shown, `variance` the per-channel variance of the mean, `passes` the passes done,
         `unconverged` and `max_ratio` the last record. No Go counterpart."""
-        import torch
-
         if max_passes < 1 or batch < 1:
             raise ValueError("max_passes and batch must be >= 1")
         if overrides and not denoise:
             raise ValueError(f"filter parameters {sorted(overrides)} given without denoise=True")
         scene = self._apply_defaults(scene)
         self.Camera.Initialize(self.width, self.height)
-        device = int(self.Devices[0] if self.Devices else self.Device)
-        where = torch.device(f"cuda:{device}")
         self.seed = self._seed()  # once: every pass draws from this stream
-        mp = _lib.accum_metric_params(**{n: v for n, v in (("tolerance", tolerance), ("floor", floor))
-                                         if v is not None})
+        mp = _lib.accum_metric_params(**_given(tolerance=tolerance, floor=floor))
         h, w = self.height, self.width
         self.passes, self.unconverged, self.max_ratio = 0, h * w, 0.0
         self.variance = np.full((h, w, 3), np.inf)
         if h * w == 0:
             return self.imageData
-        stream = torch.cuda.current_stream(where).cuda_stream
+        torch, device, where, stream = self._target()
         dev = scene._device_scene(device)
         f64 = dict(dtype=torch.float64, device=where)
         frames = torch.empty((min(batch, max_passes), h, w, 3), **f64)
         mean, m2, variance = (torch.empty((h, w, 3), **f64) for _ in range(3))
         record = torch.empty((2,), **f64)
         acc = _lib.Accum(mean.data_ptr(), m2.data_ptr(), w, h, 0, 0)
-        aov = None
-        if denoise:
-            if guides is None:
-                aov = {name: torch.empty((h, w, 3)[: 3 if ch > 1 else 2], **f64)
-                       for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1))}
-                p0 = _lib.make_params(w, h, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, self.seed, 0, h)
-                dev.render_aov_async(self.Camera._state, p0, aov["albedo"].data_ptr(), aov["normal"].data_ptr(),
-                                     aov["depth"].data_ptr(), stream=stream)
-            else:
-                aov = {}
-                for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1)):
-                    g = guides.get(name)
-                    if g is None:
-                        continue
-                    g = np.ascontiguousarray(g, dtype=np.float64)
-                    if g.shape != (h, w) + ((3,) if ch == 3 else ()):
-                        raise ValueError(f"{name} must cover the frame; got {g.shape}")
-                    aov[name] = torch.from_numpy(g).to(where)
+        aov = self._frame_guides(torch, dev, guides, where, stream) if denoise else None
         while self.passes < max_passes:
             n = min(batch, max_passes - self.passes)
-            params = _lib.make_params(w, h, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, self.seed, 0, h,
-                                      pass_=self.passes)
-            dev.render_passes_async(self.Camera._state, params, n, frames.data_ptr(), stream)
+            dev.render_passes_async(self.Camera._state, self._params(self.seed, self.passes), n, frames.data_ptr(),
+                                    stream)
             _lib.accum_fold_metric_async(acc, frames.data_ptr(), n, mp, variance.data_ptr(), record.data_ptr(),
                                          device, stream)
             rec = record.cpu().numpy().view(_lib.ACCUM_METRIC_DTYPE)[0]  # the 16-byte readback
@@ -680,21 +700,9 @@ class Tracer:  # ray/tracer.go:25-36
             self.unconverged, self.max_ratio = int(rec["unconverged"]), float(rec["max_ratio"])
             if self.passes >= 2 and self.unconverged <= fraction * (h * w):
                 break
-        shown = mean
-        if denoise:
-            dp = _lib.denoise_variance_params(w, h, **overrides)
-            nbytes = _lib.denoise_variance_workspace_bytes(dp)
-            shown = torch.empty_like(mean)
-            work = torch.empty((max(nbytes, 8) // 8,), **f64)
-            _lib.denoise_variance_async(mean.data_ptr(), variance.data_ptr(), dp, shown.data_ptr(),
-                                        work.data_ptr() if nbytes else None, nbytes,
-                                        *(aov[k].data_ptr() if aov.get(k) is not None else None
-                                          for k in ("albedo", "normal", "depth")), device=device, stream=stream)
-        rgba = torch.empty((h, w, 4), dtype=torch.uint8, device=where)
-        _lib.linear_to_srgba_async(shown.data_ptr(), h * w, rgba.data_ptr(), device, stream)
-        self.linear[:] = shown.cpu().numpy()
+        shown = self._denoise_variance_device(torch, mean, variance, aov, overrides) if denoise else mean
+        self._show(torch, shown, device, stream)
         self.variance = variance.cpu().numpy()
-        self.imageData[:] = rgba.cpu().numpy()
         return self.imageData
 
     def RenderPixels(self, scene: Scene | None, pixels, passes: int = 1, pass_: int = 0) -> np.ndarray:
@@ -704,8 +712,6 @@ class Tracer:  # ray/tracer.go:25-36
         bits of that pixel in an ordered-sum render of that pass (TRAY_FLAG_ORDERED_SUM), whichever
         other pixels are listed; an index outside the image gets zeros. For a region of interest or
         for rendering a picked pixel again. Set Seed for values that repeat. No Go counterpart."""
-        import torch
-
         if passes < 1:
             raise ValueError("passes must be >= 1")
         idx = np.ascontiguousarray(pixels)
@@ -714,16 +720,14 @@ class Tracer:  # ray/tracer.go:25-36
         idx = idx.astype(np.uint32)
         scene = self._apply_defaults(scene)
         self.Camera.Initialize(self.width, self.height)
-        device = int(self.Devices[0] if self.Devices else self.Device)
-        where = torch.device(f"cuda:{device}")
-        params = _lib.make_params(self.width, self.height, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius,
-                                  self._seed(), 0, self.height, pass_=pass_)
+        params = self._params(self._seed(), pass_)
+        torch, device, where, stream = self._target()
         n = int(idx.size)
         out = torch.empty((passes, n, 3), dtype=torch.float64, device=where)
         lst = torch.from_numpy(idx.view(np.int32)).to(where)
         scene._device_scene(device).render_pixels_async(
             self.Camera._state, params, lst.data_ptr() if n else None, n, out.data_ptr() if n else None, passes,
-            stream=torch.cuda.current_stream(where).cuda_stream)
+            stream=stream)
         return out.cpu().numpy()
 
     def RenderAdaptive(self, scene: Scene | None, max_passes: int, min_passes: int | None = None, batch: int = 4,
@@ -745,21 +749,17 @@ class Tracer:  # ray/tracer.go:25-36
         keeps it in imageData; `linear` holds the FP64 frame shown, `variance` the per-channel
         variance of the mean, `counts` the (H, W) int32 passes of each pixel, `passes` their maximum,
         `pixel_passes` their sum, `unconverged` and `max_ratio` the last record. No Go counterpart."""
-        import torch
-
         if max_passes < 1 or batch < 1:
             raise ValueError("max_passes and batch must be >= 1")
         if overrides and not denoise:
             raise ValueError(f"filter parameters {sorted(overrides)} given without denoise=True")
-        given = {n: v for n, v in (("tolerance", tolerance), ("floor", floor)) if v is not None}
-        ap = _lib.adaptive_params(max_passes=int(max_passes), dilate=int(dilate), **given)
+        ap = _lib.adaptive_params(max_passes=int(max_passes), dilate=int(dilate),
+                                  **_given(tolerance=tolerance, floor=floor))
         ap.min_passes = min(int(min_passes) if min_passes is not None else ap.min_passes, int(max_passes))
         if ap.min_passes < 1:
             raise ValueError("min_passes must be >= 1")
         scene = self._apply_defaults(scene)
         self.Camera.Initialize(self.width, self.height)
-        device = int(self.Devices[0] if self.Devices else self.Device)
-        where = torch.device(f"cuda:{device}")
         self.seed = self._seed()  # once: every pass draws from this stream
         h, w = self.height, self.width
         self.passes, self.pixel_passes, self.unconverged, self.max_ratio = 0, 0, h * w, 0.0
@@ -767,39 +767,18 @@ class Tracer:  # ray/tracer.go:25-36
         self.counts = np.zeros((h, w), dtype=np.int32)
         if h * w == 0:
             return self.imageData
-        stream = torch.cuda.current_stream(where).cuda_stream
+        torch, device, where, stream = self._target()
         dev = scene._device_scene(device)
         f64 = dict(dtype=torch.float64, device=where)
-
-        def make_params(pass_=0, flags=0):
-            return _lib.make_params(w, h, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, self.seed, 0, h,
-                                    flags=flags, pass_=pass_)
-
         mean, m2, variance = (torch.empty((h, w, 3), **f64) for _ in range(3))
         counts = torch.full((h, w), ap.min_passes, dtype=torch.int32, device=where)
-        aov = None
-        if denoise:
-            if guides is None:
-                aov = {name: torch.empty((h, w, 3)[: 3 if ch > 1 else 2], **f64)
-                       for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1))}
-                dev.render_aov_async(self.Camera._state, make_params(), aov["albedo"].data_ptr(),
-                                     aov["normal"].data_ptr(), aov["depth"].data_ptr(), stream=stream)
-            else:
-                aov = {}
-                for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1)):
-                    g = guides.get(name)
-                    if g is None:
-                        continue
-                    g = np.ascontiguousarray(g, dtype=np.float64)
-                    if g.shape != (h, w) + ((3,) if ch == 3 else ()):
-                        raise ValueError(f"{name} must cover the frame; got {g.shape}")
-                    aov[name] = torch.from_numpy(g).to(where)
+        aov = self._frame_guides(torch, dev, guides, where, stream) if denoise else None
         # The warm-up: uniform passes through the megakernel, in launches of at most `batch`.
         frames = torch.empty((min(batch, ap.min_passes), h, w, 3), **f64)
         acc = _lib.Accum(mean.data_ptr(), m2.data_ptr(), w, h, 0, 0)
         while acc.count < ap.min_passes:
             n = min(batch, ap.min_passes - acc.count)
-            dev.render_passes_async(self.Camera._state, make_params(acc.count, _lib.FLAG_ORDERED_SUM), n,
+            dev.render_passes_async(self.Camera._state, self._params(self.seed, acc.count, _lib.FLAG_ORDERED_SUM), n,
                                     frames.data_ptr(), stream)
             _lib.accum_fold_async(acc, frames.data_ptr(), n, device, stream)
         del frames
@@ -822,28 +801,16 @@ class Tracer:  # ray/tracer.go:25-36
                 break
             if values is None or values.shape[1] < n_active:  # the lists only shrink between rounds, almost
                 values = torch.empty((batch, n_active, 3), **f64)
-            dev.render_pixels_async(self.Camera._state, make_params(), active.data_ptr(), n_active, values.data_ptr(),
-                                    batch, pass_plane_ptr=counts.data_ptr(), stream=stream)
+            dev.render_pixels_async(self.Camera._state, self._params(self.seed), active.data_ptr(), n_active,
+                                    values.data_ptr(), batch, pass_plane_ptr=counts.data_ptr(), stream=stream)
             _lib.adaptive_fold_async(state, active.data_ptr(), n_active, values.data_ptr(), batch, device, stream)
         self.unconverged, self.max_ratio = int(rec["unconverged"]), float(rec["max_ratio"])
         self.pixel_passes = int(rec["pixel_passes"])
-        shown = mean
-        if denoise:
-            dp = _lib.denoise_variance_params(w, h, **overrides)
-            dbytes = _lib.denoise_variance_workspace_bytes(dp)
-            shown = torch.empty_like(mean)
-            dwork = torch.empty((max(dbytes, 8) // 8,), **f64)
-            _lib.denoise_variance_async(mean.data_ptr(), variance.data_ptr(), dp, shown.data_ptr(),
-                                        dwork.data_ptr() if dbytes else None, dbytes,
-                                        *(aov[k].data_ptr() if aov.get(k) is not None else None
-                                          for k in ("albedo", "normal", "depth")), device=device, stream=stream)
-        rgba = torch.empty((h, w, 4), dtype=torch.uint8, device=where)
-        _lib.linear_to_srgba_async(shown.data_ptr(), h * w, rgba.data_ptr(), device, stream)
-        self.linear[:] = shown.cpu().numpy()
+        shown = self._denoise_variance_device(torch, mean, variance, aov, overrides) if denoise else mean
+        self._show(torch, shown, device, stream)
         self.variance = variance.cpu().numpy()
         self.counts = counts.cpu().numpy()
         self.passes = int(self.counts.max())
-        self.imageData[:] = rgba.cpu().numpy()
         return self.imageData
 
     def RenderSequence(self, scene: Scene | None, cameras, denoise: bool = False, variance: bool = False,
@@ -909,15 +876,11 @@ class Tracer:  # ray/tracer.go:25-36
         if refill and tp.max_history < 1 + refill:
             raise ValueError(f"refill={refill} needs max_history >= {1 + refill}: no pixel could hold "
                              f"1 + refill frames (max_history is {tp.max_history})")
-        import torch
-
         scene = self._apply_defaults(scene)
         h, w = self.height, self.width
         for c in cameras:
             c.Initialize(w, h)
         object.__setattr__(self, "Camera", cameras[-1])
-        device = int(self.Devices[0] if self.Devices else self.Device)
-        where = torch.device(f"cuda:{device}")
         self.seed = self._seed()  # once: every frame is a pass of this stream
         self.age = np.zeros((h, w), dtype=np.int32)
         self.fresh, self.mean_age = [], []
@@ -927,7 +890,7 @@ class Tracer:  # ray/tracer.go:25-36
             self.refilled, self.pixel_passes = [], 0
         if h * w == 0:
             return [self.imageData.copy() for _ in cameras]
-        stream = torch.cuda.current_stream(where).cuda_stream
+        torch, device, where, stream = self._target()
         dev = scene._device_scene(device)
         f64 = dict(dtype=torch.float64, device=where)
 
@@ -945,10 +908,7 @@ class Tracer:  # ray/tracer.go:25-36
         frame = torch.empty((h, w, 3), **f64)
         records = torch.empty((len(cameras), 2), dtype=torch.int64, device=where)
         rgba = torch.empty((len(cameras), h, w, 4), dtype=torch.uint8, device=where)
-        aov = None
-        if denoise:
-            aov = {name: torch.empty((h, w, 3)[: 3 if ch > 1 else 2], **f64)
-                   for name, ch in (("albedo", 3), ("normal", 3), ("depth", 1))}
+        aov = self._guide_buffers(torch, where) if denoise else None
         var_plane = torch.empty((h, w, 3), **f64) if variance else None
         if refill:
             ap = _lib.adaptive_params(tolerance=rt, min_passes=1 + refill, max_passes=int(tp.max_history),
@@ -958,15 +918,9 @@ class Tracer:  # ray/tracer.go:25-36
             active = torch.empty((h * w,), dtype=torch.int32, device=where)
             arecord = torch.empty((4,), **f64)
             values = torch.empty((refill * h * w * 3,), **f64)  # frame 0 lists every pixel
-        if denoise and variance:
-            dp = _lib.denoise_variance_params(w, h)
-            dbytes = _lib.denoise_variance_workspace_bytes(dp)
-            dwork = torch.empty((max(dbytes, 8) // 8,), **f64)
-            filtered = torch.empty((h, w, 3), **f64)
         stride = 1 + refill  # frame k owns the passes k * stride .. (k + 1) * stride - 1
         for k, cam in enumerate(cameras):
-            params = _lib.make_params(w, h, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, self.seed, 0, h,
-                                      pass_=k * stride)
+            params = self._params(self.seed, k * stride)
             dev.render_async(cam._state, params, frame.data_ptr(), None, stream)
             out = states[k & 1]
             if variance:
@@ -984,24 +938,17 @@ class Tracer:  # ray/tracer.go:25-36
                 n_active = int(arecord.cpu().numpy().view(_lib.ADAPTIVE_RECORD_DTYPE)[0]["n_active"])  # 32 bytes
                 self.refilled.append(n_active)
                 if n_active:
-                    rp = _lib.make_params(w, h, self.MaxDepth, self.NumRaysPerPixel, self.RayRadius, self.seed, 0, h,
-                                          pass_=k * stride + 1)
-                    dev.render_pixels_async(cam._state, rp, active.data_ptr(), n_active, values.data_ptr(), refill,
-                                            stream=stream)
+                    dev.render_pixels_async(cam._state, self._params(self.seed, k * stride + 1), active.data_ptr(),
+                                            n_active, values.data_ptr(), refill, stream=stream)
                     _lib.adaptive_fold_async(ast, active.data_ptr(), n_active, values.data_ptr(), refill, device,
                                              stream)
                     _lib.temporal_var_variance_async(out[1], active.data_ptr(), n_active, var_plane.data_ptr(),
                                                      device, stream)
             shown = out[0]["colour"]
             if denoise:
-                dev.render_aov_async(cam._state, params, aov["albedo"].data_ptr(), aov["normal"].data_ptr(),
-                                     aov["depth"].data_ptr(), stream=stream)
+                dev.render_aov_async(cam._state, params, *_guide_ptrs(aov), stream=stream)
                 if variance:
-                    _lib.denoise_variance_async(shown.data_ptr(), var_plane.data_ptr(), dp, filtered.data_ptr(),
-                                                dwork.data_ptr() if dbytes else None, dbytes,
-                                                aov["albedo"].data_ptr(), aov["normal"].data_ptr(),
-                                                aov["depth"].data_ptr(), device=device, stream=stream)
-                    shown = filtered
+                    shown = self._denoise_variance_device(torch, shown, var_plane, aov, {})
                 else:
                     shown = self._denoise_device(torch, shown, aov, {})
             _lib.linear_to_srgba_async(shown.data_ptr(), h * w, rgba[k].data_ptr(), device, stream)
