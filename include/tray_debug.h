@@ -86,6 +86,19 @@ int tray_debug_plain_instance(uint32_t facts, int32_t rays_per_pixel, int32_t ti
 /* Launches (one per band) that took the plain-frame instance since the library was loaded. */
 int tray_debug_plain_launches(uint64_t *count_out);
 
+/* The kernel families that find their hits outside the megakernel, for tray_debug_query_traversal. */
+#define TRAY_QUERY_KIND_PLAIN 0    /* tray_scene_hit_async, tray_scene_occluded_async, tray_ray_color_async,
+                                      tray_render_aov_async */
+#define TRAY_QUERY_KIND_PIXELS 1   /* tray_render_pixels_async */
+#define TRAY_QUERY_KIND_TEMPORAL 2 /* tray_temporal_step_async, tray_temporal_var_step_async */
+/* The library's own choice, for a launch of `kind` on a scene with a BVH and without
+ * TRAY_FLAG_LINEAR_SCAN, between traversing the tree (*bvh_out = 1) and the linear scan for every
+ * ray (0): the traversal stacks, 1 KiB per slot, must fit into 64 KiB of LDS beside what the kernel
+ * holds there itself (nothing / 8 KiB of parked colours / 64 bytes of the record's reduction).
+ * `stack_depth` is tray_scene_info's; the stacks hold 3 slots more. Both sides give the same bits.
+ * Host only: no device is touched. */
+int tray_debug_query_traversal(int32_t kind, int32_t stack_depth, int32_t *bvh_out);
+
 #ifdef __cplusplus
 }
 #endif

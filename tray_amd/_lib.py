@@ -384,13 +384,15 @@ assert ctypes.sizeof(TemporalVarState) == 48
 
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
 DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear", "tray_debug_progress_counts", "tray_debug_plain_instance",
-                 "tray_debug_plain_launches")
+                 "tray_debug_plain_launches", "tray_debug_query_traversal")
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
                "primary_candidates", "resolve_staged", "wave_chunks", "scene_contexts", "grid_reserve",
                "work_order", "coop_lanes", "plain_instance")
 # tray_debug_plain_instance's `facts` bits (TRAY_PLAIN_FACT_*).
 PLAIN_FACTS = {"bvh": 1, "stats": 2, "progress": 4, "stack_spill": 8, "segments": 16, "counting": 32,
                "candidates": 64, "work_order": 128}
+# tray_debug_query_traversal's kinds (TRAY_QUERY_KIND_*).
+QUERY_KINDS = {"plain": 0, "pixels": 1, "temporal": 2}
 
 # tray_progress_fn: void (*)(int32_t rows, void *user)
 PROGRESS_FN = ctypes.CFUNCTYPE(None, ctypes.c_int32, ctypes.c_void_p)
@@ -530,6 +532,8 @@ def lib(path: str | None = None) -> ctypes.CDLL:
     if hasattr(L, "tray_debug_plain_instance"):  # absent from older builds (A/B tools)
         L.tray_debug_plain_instance.argtypes = [ctypes.c_uint32] + [i32] * 7 + [ctypes.POINTER(i32)]
         L.tray_debug_plain_launches.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(L, "tray_debug_query_traversal"):  # absent from older builds (A/B tools)
+        L.tray_debug_query_traversal.argtypes = [i32, i32, ctypes.POINTER(i32)]
     _libs[path] = L
     return L
 
@@ -594,6 +598,14 @@ def plain_launches() -> int:
     n = ctypes.c_uint64(0)
     check(lib().tray_debug_plain_launches(ctypes.byref(n)))
     return int(n.value)
+
+
+def query_traversal(kind: str, stack_depth: int) -> bool:
+    """tray_debug_query_traversal: whether a launch of `kind` (a name of QUERY_KINDS) on a scene with
+    a BVH of tray_scene_info's `stack_depth` traverses the tree (True) or scans. Host only."""
+    out = ctypes.c_int32(-1)
+    check(lib().tray_debug_query_traversal(QUERY_KINDS[kind], stack_depth, ctypes.byref(out)))
+    return out.value == 1
 
 
 def clear_debug_knobs(lib_path: str | None = None) -> None:

@@ -27,6 +27,7 @@
 #include "rng.hpp"
 #include "tray_kernel.hpp"
 #include "tray_query.hpp"
+#include "tray_query_device.hpp"  // query_takes_tree, for tray_debug_query_traversal
 
 namespace tray {
 
@@ -353,6 +354,19 @@ int tray_debug_plain_instance(uint32_t facts, int32_t rays_per_pixel, int32_t ti
                                     acc, lds_mode)
                      ? 1
                      : 0;
+    return TRAY_OK;
+}
+
+static_assert(TRAY_QUERY_KIND_PLAIN == kQueryPlain && TRAY_QUERY_KIND_PIXELS == kQueryPixels &&
+                  TRAY_QUERY_KIND_TEMPORAL == kQueryTemporal,
+              "tray_debug.h names the kinds of tray_query_device.hpp");
+
+int tray_debug_query_traversal(int32_t kind, int32_t stack_depth, int32_t* bvh_out) {
+    if (!bvh_out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null argument");
+    if (kind < TRAY_QUERY_KIND_PLAIN || kind > TRAY_QUERY_KIND_TEMPORAL)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "unknown query kind");
+    if (stack_depth < 0 || stack_depth > (1 << 20)) return fail(TRAY_ERR_INVALID_ARGUMENT, "stack_depth out of range");
+    *bvh_out = query_takes_tree(static_cast<QueryKind>(kind), stack_depth + kStackSlack) ? 1 : 0;
     return TRAY_OK;
 }
 

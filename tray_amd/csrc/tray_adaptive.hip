@@ -48,7 +48,6 @@ struct PixelArgs {
     uint32_t rounds;         // ceil(r / g)
     double inv_spp;          // RN(1 / r), the host's quotient (colorSumDiv, ray/tracer.go:123)
 };
-constexpr size_t kPixelStaticLds = 8 * 1024;  // an upper bound of the kernel's static LDS (7196 bytes)
 
 // threadIdx.x, opaque to the optimiser: what is derived from it is derived again at each use
 // instead of being held in registers.
@@ -186,11 +185,8 @@ hipError_t launch_render_pixels(KernelParams p, bool use_bvh, double bound, cons
     if (n_pixels == 0 || n_passes == 0) return hipSuccess;
     p.div_tile_rows = make_fastdiv((uint32_t)std::max(p.tile_rows, 1));  // row_of
     size_t lds = 0;
-    QueryArgs q = query_args(p, use_bvh, bound, nullptr, 0, lds);
-    if (lds + kPixelStaticLds > kQueryLdsMax) {  // stacks that do not fit beside the parked colours: the scan
-        q.use_bvh = 0;
-        lds = 0;
-    }
+    // Stacks that do not fit beside the parked colours: the scan (query_takes_tree).
+    const QueryArgs q = query_args(p, use_bvh, bound, nullptr, 0, lds, kQueryPixels);
     PixelArgs a{};
     a.pixels = pixels;
     a.plane = pass_plane;

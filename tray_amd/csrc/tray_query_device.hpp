@@ -158,16 +158,34 @@ __device__ __forceinline__ QStack lane_stack() {
 }
 
 // The stacks of one workgroup; the dynamic-LDS default limit (64 KB) bounds them.
-static size_t query_stack_bytes(int32_t stack_cap) { return (size_t)stack_cap * kQueryBlock * sizeof(uint32_t); }
+inline size_t query_stack_bytes(int32_t stack_cap) { return (size_t)stack_cap * kQueryBlock * sizeof(uint32_t); }
 constexpr size_t kQueryLdsMax = 64 * 1024;
 
-static QueryArgs query_args(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays, uint32_t n,
-                            size_t& lds) {
+// The kernel families that find their hits through query_hit / query_occluded, by the static
+// LDS their kernels hold beside the stacks (the values of TRAY_QUERY_KIND_*, include/tray_debug.h).
+enum QueryKind : int32_t {
+    kQueryPlain = 0,     // hit, occluded, ray colour, feature buffers: the stacks alone
+    kQueryPixels = 1,    // render_pixels_kernel (tray_adaptive.hip): the parked colours
+    kQueryTemporal = 2,  // temporal_step_kernel (tray_temporal.hip): the record's reduction
+};
+constexpr size_t kPixelStaticLds = 8 * 1024;  // an upper bound of render_pixels_kernel's static LDS (7196 bytes)
+constexpr size_t kTemporalStaticLds = 64;     // temporal_step_kernel's red[2][4]
+
+// Does a launch of `kind` on a scene with a tree traverse it (true), or does every ray take
+// the linear scan because the stacks do not fit into LDS beside the kernel's own? The one
+// place that decides it: query_args for every launcher, tray_debug_query_traversal for tests.
+inline bool query_takes_tree(QueryKind kind, int32_t stack_cap) {
+    const size_t beside = kind == kQueryPixels ? kPixelStaticLds : kind == kQueryTemporal ? kTemporalStaticLds : 0;
+    return query_stack_bytes(stack_cap) + beside <= kQueryLdsMax;
+}
+
+inline QueryArgs query_args(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays, uint32_t n,
+                            size_t& lds, QueryKind kind = kQueryPlain) {
     QueryArgs q{};
     q.rays = rays;
     q.n = n;
     lds = query_stack_bytes(p.stack_cap);
-    q.use_bvh = use_bvh && p.n_nodes > 0 && lds <= kQueryLdsMax ? 1 : 0;
+    q.use_bvh = use_bvh && p.n_nodes > 0 && query_takes_tree(kind, p.stack_cap) ? 1 : 0;
     if (!q.use_bvh) lds = 0;
     q.bound = bound;
     q.t_end = __builtin_inf();

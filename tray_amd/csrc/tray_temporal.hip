@@ -28,7 +28,6 @@
 namespace tray {
 
 constexpr uint32_t kTileX = 32, kTileY = kQueryBlock / kTileX;
-constexpr size_t kTemporalStaticLds = 64;  // red[2][4] below
 
 // The previous camera as the projection needs it: what does not depend on the pixel is
 // worked out once on the host (same operations, same order, no contraction there either).
@@ -88,6 +87,7 @@ __host__ __device__ inline double dot3(const double u[3], const double v[3]) {
 template <bool kM2>
 __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaunch L) {
     __shared__ unsigned long long red[2][kQueryBlock / 64];
+    static_assert(sizeof(red) <= kTemporalStaticLds, "query_takes_tree counts this kernel's static LDS");
     const KernelParams& p = L.p;
     const uint32_t width = (uint32_t)p.width, height = (uint32_t)p.height;
     const uint32_t tile_y = blockIdx.x / L.a.tiles_x, tile_x = blockIdx.x - tile_y * L.a.tiles_x;
@@ -228,11 +228,8 @@ hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, cons
                                 double* variance, tray_temporal_record* record, hipStream_t stream) {
     if (out.width <= 0 || out.height <= 0) return hipSuccess;
     size_t lds = 0;
-    QueryArgs q = query_args(p, use_bvh, bound, nullptr, 0, lds);
-    if (lds + kTemporalStaticLds > kQueryLdsMax) {  // stacks that do not fit beside the reduction: the scan
-        q.use_bvh = 0;
-        lds = 0;
-    }
+    // Stacks that do not fit beside the reduction: the scan (query_takes_tree).
+    const QueryArgs q = query_args(p, use_bvh, bound, nullptr, 0, lds, kQueryTemporal);
     TemporalArgs a{};
     a.frame = frame;
     a.out = plain_state(out);
