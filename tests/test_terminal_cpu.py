@@ -83,7 +83,10 @@ def np_nearest(src, dw, dh):
 
 
 SIZES = [((45, 80), (12, 20)), ((90, 160), (45, 80)), ((720, 1280), (48, 160)), ((37, 53), (10, 11)),
-         ((64, 64), (64, 13)), ((9, 200), (9, 7)), ((5, 5), (1, 1)), ((33, 47), (32, 46))]
+         ((64, 64), (64, 13)), ((9, 200), (9, 7)), ((5, 5), (1, 1)), ((33, 47), (32, 46)),
+         # enlarging (newDistrib's other branch: the support stays 1, two taps) and ratio 1 (one tap of
+         # weight 1): both axes, one pixel, one axis growing while the other shrinks, the same size
+         ((5, 7), (12, 20)), ((1, 1), (3, 4)), ((9, 4), (4, 9)), ((1, 300), (7, 3)), ((3, 2), (3, 2))]
 
 
 @pytest.mark.parametrize("src_hw,dst_hw", SIZES)
