@@ -49,7 +49,10 @@
 #ifndef TRAY_DEBUG_H
 #define TRAY_DEBUG_H
 
+#include <stddef.h>
 #include <stdint.h>
+
+#include "tray.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -98,6 +101,23 @@ int tray_debug_plain_launches(uint64_t *count_out);
  * `stack_depth` is tray_scene_info's; the stacks hold 3 slots more. Both sides give the same bits.
  * Host only: no device is touched. */
 int tray_debug_query_traversal(int32_t kind, int32_t stack_depth, int32_t *bvh_out);
+
+/* A synchronous copy of the scene's BVH nodes as they are on the device, for the tests of
+ * tray_scene_update.h: n_nodes (tray_scene_info) records of 128 bytes, Bvh4Node of
+ * tray_amd/csrc/bvh.hpp: float box[3][2][4] (per axis the low and the high planes of the four child
+ * slots; an unused slot has +inf / -inf), uint32 ref[4] (an inner node's index, 0x8000 | a leaf's
+ * index, or 0xFFFF for an unused slot), uint32 pad[4]. Waits for the renders and updates enqueued
+ * on the scene. *bytes_out receives the size of the array, 0 for a scene without a tree; the copy is
+ * made when capacity_bytes holds it (TRAY_ERR_INVALID_ARGUMENT when it does not; a NULL nodes_out with
+ * capacity 0 asks for the size alone). */
+int tray_debug_scene_nodes(tray_scene_t scene, void *nodes_out, size_t capacity_bytes, size_t *bytes_out);
+/* What a leaf reference of those nodes leads to, which no update changes: leaves_out receives, per
+ * leaf, (first slot << 3) | sphere count, and slots_out, per slot of the tree, the list index of the
+ * sphere kept there (the out-of-tree spheres hold the last slots). *n_leaves_out and *n_slots_out
+ * receive the counts, both 0 without a tree; each array is copied when its capacity (in entries)
+ * holds it and its pointer is not NULL. Synchronous. */
+int tray_debug_scene_leaves(tray_scene_t scene, int32_t *leaves_out, int32_t leaves_capacity, int32_t *slots_out,
+                            int32_t slots_capacity, int32_t *n_leaves_out, int32_t *n_slots_out);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,9 @@ have no meaning here).
     python -m tray_amd -r 4 -orbit 8 -variance [-refill [R]] [-denoise] ...  # the same, carrying M2: R more passes
                                           # for the fresh pixels of each frame, and the variance-guided filter
                                           # (include/tray_temporal_variance.h)
+    python -m tray_amd -r 16 -bounce 8 [-denoise] ...  # the small spheres hop: one upload, then per frame the
+                                          # spheres moved and the BVH refitted on the device
+                                          # (include/tray_scene_update.h)
 """
 from __future__ import annotations
 
@@ -79,6 +82,10 @@ def main(argv=None) -> int:
                     help="with -orbit -variance: R more passes per frame for the pixels that hold fewer than 1 + R "
                          f"frames and their neighbours (default R when given without a number: {ray.REFILL_DEFAULT}); "
                          "prints the refilled pixels per frame")
+    ap.add_argument("-bounce", type=int, default=0, metavar="N",
+                    help="render N frames in which the small spheres hop (y = R + |sin| of a phase per sphere), "
+                         "moved in place on the device with the BVH refitted (include/tray_scene_update.h); prints "
+                         "per frame whether the update was applied and saves the last frame; -denoise applies")
     ap.add_argument("-ansi", action="store_true",
                     help="render at -s x the terminal size and draw it in the terminal (main.go:86-131)")
     ap.add_argument("-s", type=float, default=4, help="supersampling factor of -ansi")
@@ -97,7 +104,14 @@ def main(argv=None) -> int:
         ap.error("-variance and -refill go with -orbit N")
     if a.refill < 0 or (a.refill and not a.variance):
         ap.error("-refill needs R >= 0 and -variance")
-    if a.orbit:
+    if a.bounce < 0 or (a.bounce and (a.orbit or a.passes or a.adaptive)):
+        ap.error("-bounce needs N >= 1 and goes with none of -orbit, -passes and -adaptive")
+    if a.bounce:
+        img = t.RenderAnimation(scene, ray.Bounce(scene, a.bounce), denoise=a.denoise)[-1]
+        for k, applied in enumerate(t.applied):
+            print(f"frame {k}: {'moved in place' if applied else 'refused: uploaded afresh'}")
+        samples *= a.bounce
+    elif a.orbit:
         cameras = [ray.Orbit(t.Camera, k * a.orbit_step) for k in range(a.orbit)]
         if a.variance:
             img = t.RenderSequence(scene, cameras, denoise=a.denoise, variance=True, refill=a.refill)[-1]

@@ -382,9 +382,28 @@ class TemporalVarState(ctypes.Structure):
 
 assert ctypes.sizeof(TemporalVarState) == 48
 
+# include/tray_scene_update.h: new centres and radii for an uploaded scene, its BVH refitted on the
+# device (in none of the lists above).
+SCENE_UPDATE_EXPORTS = ("tray_scene_update_async", "tray_scene_update")
+
+
+class SceneUpdateRecord(ctypes.Structure):
+    _fields_ = [("applied", ctypes.c_int32), ("n_refused", ctypes.c_int32), ("first_refused", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("extent", ctypes.c_double), ("bound", ctypes.c_double)]
+
+
+assert ctypes.sizeof(SceneUpdateRecord) == 32
+SCENE_UPDATE_RECORD_DTYPE = np.dtype([("applied", "<i4"), ("n_refused", "<i4"), ("first_refused", "<i4"),
+                                      ("reserved", "<i4"), ("extent", "<f8"), ("bound", "<f8")])
+assert SCENE_UPDATE_RECORD_DTYPE.itemsize == 32
+# tray_debug_scene_nodes: Bvh4Node of tray_amd/csrc/bvh.hpp, [axis][low, high][child slot].
+NODE_DTYPE = np.dtype([("box", "<f4", (3, 2, 4)), ("ref", "<u4", (4,)), ("pad", "<u4", (4,))])
+assert NODE_DTYPE.itemsize == 128
+
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
 DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear", "tray_debug_progress_counts", "tray_debug_plain_instance",
-                 "tray_debug_plain_launches", "tray_debug_query_traversal")
+                 "tray_debug_plain_launches", "tray_debug_query_traversal", "tray_debug_scene_nodes",
+                 "tray_debug_scene_leaves")
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
                "primary_candidates", "resolve_staged", "wave_chunks", "scene_contexts", "grid_reserve",
                "work_order", "coop_lanes", "plain_instance")
@@ -523,6 +542,12 @@ def lib(path: str | None = None) -> ctypes.CDLL:
                                                    ctypes.POINTER(TemporalVarState), vp, vp, vp]
         L.tray_temporal_var_variance_async.argtypes = [ctypes.POINTER(TemporalVarState), vp, ctypes.c_int64, vp, i32,
                                                        vp]
+    if hasattr(L, "tray_scene_update_async"):  # include/tray_scene_update.h; absent from older builds (A/B tools)
+        L.tray_scene_update_async.argtypes = [vp, vp, i32, vp, vp]
+        L.tray_scene_update.argtypes = [vp, vp, i32, ctypes.POINTER(SceneUpdateRecord)]
+    if hasattr(L, "tray_debug_scene_nodes"):
+        L.tray_debug_scene_nodes.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+        L.tray_debug_scene_leaves.argtypes = [vp, vp, i32, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     if hasattr(L, "tray_debug_set"):  # absent from older builds (A/B tools)
         L.tray_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int64]
         L.tray_debug_clear.argtypes = [ctypes.c_char_p]
@@ -1095,6 +1120,53 @@ class DeviceScene:
         if rc != TRAY_OK:
             raise TrayError(rc, self.L.tray_last_error().decode())
         return out
+
+    def update_async(self, geometry_ptr: int, n: int, record_ptr: int, stream: int | None = None) -> None:
+        """tray_scene_update_async: new centres and radii, n x {cx, cy, cz, radius} f64 on the device, and
+        the BVH refitted to them, enqueued on `stream`; record_ptr -> a 32-byte tray_scene_update_record
+        (SCENE_UPDATE_RECORD_DTYPE) on the device, whose `applied` is 0 when the update was refused."""
+        rc = self.L.tray_scene_update_async(self.handle, geometry_ptr, int(n), record_ptr, stream)
+        if rc != TRAY_OK:
+            raise TrayError(rc, self.L.tray_last_error().decode())
+
+    def update(self, geometry) -> SceneUpdateRecord:
+        """tray_scene_update: the same from a host (n, 4) array {cx, cy, cz, radius}, synchronous."""
+        g = np.ascontiguousarray(geometry, dtype=np.float64)
+        if g.ndim != 2 or g.shape[1] != 4:
+            raise ValueError("geometry must be (n, 4): cx, cy, cz, radius")
+        rec = SceneUpdateRecord()
+        rc = self.L.tray_scene_update(self.handle, g.ctypes.data if len(g) else None, len(g), ctypes.byref(rec))
+        if rc != TRAY_OK:
+            raise TrayError(rc, self.L.tray_last_error().decode())
+        return rec
+
+    def nodes(self) -> np.ndarray:
+        """tray_debug_scene_nodes: the scene's BVH nodes as they are on the device, a NODE_DTYPE
+        array (empty without a tree). Waits for the scene's enqueued renders and updates."""
+        size = ctypes.c_size_t(0)
+        rc = self.L.tray_debug_scene_nodes(self.handle, None, 0, ctypes.byref(size))
+        if rc != TRAY_OK:
+            raise TrayError(rc, self.L.tray_last_error().decode())
+        out = np.zeros(size.value // NODE_DTYPE.itemsize, dtype=NODE_DTYPE)
+        if size.value:
+            rc = self.L.tray_debug_scene_nodes(self.handle, out.ctypes.data, out.nbytes, ctypes.byref(size))
+            if rc != TRAY_OK:
+                raise TrayError(rc, self.L.tray_last_error().decode())
+        return out
+
+    def leaves(self):
+        """tray_debug_scene_leaves: (leaves, slots), int32 arrays: per leaf (first slot << 3) | count,
+        per slot of the tree the list index of its sphere. Both empty without a tree."""
+        nl, ns = ctypes.c_int32(0), ctypes.c_int32(0)
+        rc = self.L.tray_debug_scene_leaves(self.handle, None, 0, None, 0, ctypes.byref(nl), ctypes.byref(ns))
+        if rc != TRAY_OK:
+            raise TrayError(rc, self.L.tray_last_error().decode())
+        leaves, slots = np.zeros(nl.value, dtype=np.int32), np.zeros(ns.value, dtype=np.int32)
+        rc = self.L.tray_debug_scene_leaves(self.handle, leaves.ctypes.data, len(leaves), slots.ctypes.data, len(slots),
+                                            ctypes.byref(nl), ctypes.byref(ns))
+        if rc != TRAY_OK:
+            raise TrayError(rc, self.L.tray_last_error().decode())
+        return leaves, slots
 
     def release(self) -> None:
         if self.handle:

@@ -28,6 +28,7 @@
 #include "tray_kernel.hpp"
 #include "tray_query.hpp"
 #include "tray_query_device.hpp"  // query_takes_tree, for tray_debug_query_traversal
+#include "tray_scene_update.hpp"
 
 namespace tray {
 
@@ -220,9 +221,11 @@ struct LaunchCtx {
 // (on the device, hipStreamWaitEvent) for the least recently used one.
 constexpr int kSceneContexts = 4;
 
-// A scene resident on one device. Its arrays are read-only after the upload;
-// everything a render writes lives in a launch context (above), taken under the
-// scene's mutex for the time it takes to enqueue the render.
+// A scene resident on one device. Its arrays are read-only after the upload, but
+// for tray_scene_update_async (include/tray_scene_update.h), which rewrites the
+// centres, radii and boxes in stream order; everything a render writes lives in a
+// launch context (above), taken under the scene's mutex for the time it takes to
+// enqueue the render.
 struct tray_scene_s {
     int32_t device;
     int32_t n;
@@ -251,6 +254,14 @@ struct tray_scene_s {
     std::mutex mu;  // guards ctx and launches
     std::vector<LaunchCtx*> ctx;
     uint64_t launches;
+    // tray_scene_update_async: the child references of the nodes (host copy, n_nodes x
+    // kBvhWidth), the level schedule built from them at the first update (a device buffer
+    // of the scene's own, outside the arena) and the event recorded after the last update.
+    std::vector<uint32_t> refs;
+    uint32_t* schedule;
+    int32_t n_levels;
+    hipEvent_t updated;
+    bool update_recorded;
 };
 
 using namespace tray;
@@ -540,6 +551,14 @@ int tray_scene_upload(const tray_sphere* spheres, int32_t n, const tray_backgrou
             *parts[i].dst = parts[i].bytes ? static_cast<uint8_t*>(sc->arena) + offsets[i] : nullptr;
     }
     if (has_bvh) sc->ovf_bytes = bvh_stack_overflow_bytes(bvh.stack_max + kStackSlack, device);
+    sc->schedule = nullptr;
+    sc->n_levels = 0;
+    sc->updated = nullptr;
+    sc->update_recorded = false;
+    if (has_bvh) {
+        sc->refs.reserve(bvh.nodes.size() * kBvhWidth);
+        for (const Bvh4Node& node : bvh.nodes) sc->refs.insert(sc->refs.end(), node.ref, node.ref + kBvhWidth);
+    }
     if (e != hipSuccess) {
         (void)hipFree(sc->arena);
         delete sc;
@@ -582,6 +601,9 @@ int tray_scene_release(tray_scene_t sc) {
         for (LaunchCtx* c : sc->ctx) free_ctx(c);  // waits for the renders still enqueued
         sc->ctx.clear();
     }
+    if (sc->update_recorded) (void)hipEventSynchronize(sc->updated);  // an update still enqueued
+    if (sc->updated) (void)hipEventDestroy(sc->updated);
+    if (sc->schedule) (void)hipFree(sc->schedule);
     if (sc->arena) (void)hipFree(sc->arena);
     delete sc;
     return TRAY_OK;
@@ -1269,6 +1291,125 @@ int tray_temporal_var_variance_async(const tray_temporal_var_state* state, const
     TRAY_HIP(launch_temporal_variance(state->m2, state->age, (uint32_t)image, pixels_device,
                                       pixels_device ? (uint32_t)n_pixels : 0u, variance_device,
                                       static_cast<hipStream_t>(stream)));
+    return TRAY_OK;
+}
+
+// ---- moving spheres (include/tray_scene_update.h) ---------------------------------
+int tray_scene_update_async(tray_scene_t sc, const double* geometry_device, int32_t n_spheres,
+                            tray_scene_update_record* record_device, void* stream_arg) {
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    if (!geometry_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null geometry");
+    if (!record_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null record");
+    if (n_spheres != sc->n)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "n_spheres is " + std::to_string(n_spheres) + ", the scene has " +
+                                                   std::to_string(sc->n) + ": an update keeps the sphere count");
+    const hipStream_t stream = static_cast<hipStream_t>(stream_arg);
+    TRAY_HIP(hipSetDevice(sc->device));
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if (sc->has_bvh && !sc->schedule) {  // the first update: topology only, so built once
+        int32_t n_levels = 0;
+        const std::vector<uint32_t> sched = refit_schedule(sc->refs.data(), sc->n_nodes, &n_levels);
+        uint32_t* dev = nullptr;
+        TRAY_HIP(hipMalloc(reinterpret_cast<void**>(&dev), sched.size() * sizeof(uint32_t)));
+        const hipError_t e = hipMemcpy(dev, sched.data(), sched.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(dev);
+            return hip_fail(e, "level schedule");
+        }
+        sc->schedule = dev;
+        sc->n_levels = n_levels;
+    }
+    if (!sc->updated) TRAY_HIP(hipEventCreateWithFlags(&sc->updated, hipEventDisableTiming));
+    // Renders enqueued so far read the old geometry: the update waits for each context's last
+    // one (on the device). Their candidate lists and work orders were the old geometry's.
+    for (LaunchCtx* c : sc->ctx) {
+        if (c->launched && c->last_stream != stream) TRAY_HIP(hipStreamWaitEvent(stream, c->done, 0));
+        c->cand_valid = c->order_valid = false;
+    }
+    SceneUpdateArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = geometry_device;
+    a.n = sc->n;
+    a.geo = sc->geo;
+    a.mat = sc->mat;
+    a.has_bvh = sc->has_bvh ? 1 : 0;
+    if (sc->has_bvh) {
+        a.n_slots = sc->n_slots;
+        a.bgeo = sc->bgeo;
+        a.bmat = sc->bmat;
+        a.bidx = sc->bidx;
+        a.nodes = sc->nodes;
+        a.n_nodes = sc->n_nodes;
+        a.leaves = sc->leaves;
+        a.schedule = sc->schedule;
+        a.n_levels = sc->n_levels;
+        a.bound = sc->bvh_bound;
+        a.pad = 4e-6 * sc->bvh_bound;  // Builder::pad (tray_bvh.cpp)
+    }
+    a.record = record_device;
+    TRAY_HIP(launch_scene_update(a, stream));
+    const hipError_t e = hipEventRecord(sc->updated, stream);
+    if (e != hipSuccess) {  // nothing marks the update's end: wait for it here
+        (void)hipStreamSynchronize(stream);
+        return hip_fail(e, "hipEventRecord");
+    }
+    sc->update_recorded = true;
+    return TRAY_OK;
+}
+
+int tray_scene_update(tray_scene_t sc, const double* geometry_host, int32_t n_spheres,
+                      tray_scene_update_record* record_out) {
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    if (!geometry_host) return fail(TRAY_ERR_INVALID_ARGUMENT, "null geometry");
+    if (!record_out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null record");
+    if (n_spheres != sc->n)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "n_spheres is " + std::to_string(n_spheres) + ", the scene has " +
+                                                   std::to_string(sc->n) + ": an update keeps the sphere count");
+    TRAY_HIP(hipSetDevice(sc->device));
+    const size_t geo_bytes = sizeof(double) * 4 * (size_t)n_spheres;
+    uint8_t* staging = nullptr;  // the record, then the geometry
+    TRAY_HIP(hipMalloc(reinterpret_cast<void**>(&staging), sizeof(tray_scene_update_record) + geo_bytes + 32));
+    tray_scene_update_record* record_device = reinterpret_cast<tray_scene_update_record*>(staging);
+    double* geometry_device = reinterpret_cast<double*>(staging + sizeof(tray_scene_update_record));
+    hipError_t e = geo_bytes ? hipMemcpy(geometry_device, geometry_host, geo_bytes, hipMemcpyHostToDevice) : hipSuccess;
+    int rc = e == hipSuccess ? tray_scene_update_async(sc, geometry_device, n_spheres, record_device, nullptr)
+                             : hip_fail(e, "geometry staging");
+    if (rc == TRAY_OK) {
+        e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess) e = hipMemcpy(record_out, record_device, sizeof(*record_out), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "scene update");
+    }
+    (void)hipFree(staging);
+    return rc;
+}
+
+int tray_debug_scene_nodes(tray_scene_t sc, void* nodes_out, size_t capacity_bytes, size_t* bytes_out) {
+    if (!sc || !bytes_out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t bytes = sc->has_bvh ? sizeof(Bvh4Node) * (size_t)sc->n_nodes : 0;
+    *bytes_out = bytes;
+    if (!nodes_out && capacity_bytes == 0) return TRAY_OK;  // the size alone
+    if (!nodes_out || capacity_bytes < bytes) return fail(TRAY_ERR_INVALID_ARGUMENT, "node buffer too small");
+    if (bytes == 0) return TRAY_OK;
+    TRAY_HIP(hipSetDevice(sc->device));
+    std::lock_guard<std::mutex> lk(sc->mu);
+    for (LaunchCtx* c : sc->ctx)
+        if (c->launched) TRAY_HIP(hipEventSynchronize(c->done));
+    if (sc->update_recorded) TRAY_HIP(hipEventSynchronize(sc->updated));
+    TRAY_HIP(hipMemcpy(nodes_out, sc->nodes, bytes, hipMemcpyDeviceToHost));
+    return TRAY_OK;
+}
+
+int tray_debug_scene_leaves(tray_scene_t sc, int32_t* leaves_out, int32_t leaves_capacity, int32_t* slots_out,
+                            int32_t slots_capacity, int32_t* n_leaves_out, int32_t* n_slots_out) {
+    if (!sc || !n_leaves_out || !n_slots_out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null argument");
+    const int32_t n_leaves = sc->has_bvh ? sc->n_leaves : 0, n_slots = sc->has_bvh ? sc->n_slots : 0;
+    *n_leaves_out = n_leaves;
+    *n_slots_out = n_slots;
+    TRAY_HIP(hipSetDevice(sc->device));
+    if (leaves_out && n_leaves > 0 && leaves_capacity >= n_leaves)
+        TRAY_HIP(hipMemcpy(leaves_out, sc->leaves, sizeof(int32_t) * (size_t)n_leaves, hipMemcpyDeviceToHost));
+    if (slots_out && n_slots > 0 && slots_capacity >= n_slots)
+        TRAY_HIP(hipMemcpy(slots_out, sc->bidx, sizeof(int32_t) * (size_t)n_slots, hipMemcpyDeviceToHost));
     return TRAY_OK;
 }
 

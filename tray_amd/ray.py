@@ -123,6 +123,61 @@ class Scene:  # ray/objects.go:32-35
         self._uploaded[device] = (key, dev)
         return dev
 
+    def _geometry(self) -> np.ndarray:
+        """(n, 4) float64: centre and radius per object, as to_array() flattens them."""
+        arr = self.to_array()
+        return np.ascontiguousarray(np.concatenate([arr["center"].reshape(-1, 3), arr["radius"].reshape(-1, 1)],
+                                                   axis=1))
+
+    def _set_geometry(self, geometry: np.ndarray) -> None:
+        for o, g in zip(self.Objects, geometry):
+            o.Center = (float(g[0]), float(g[1]), float(g[2]))
+            o.Radius = float(g[3])
+
+    def _adopt(self, device: int, dev: "_lib.DeviceScene | None") -> None:
+        """`dev` now holds the scene as Objects and Background describe it (None: nothing does)."""
+        if dev is None:
+            self._uploaded.pop(device, None)
+        else:
+            self._uploaded[device] = (self.to_array().tobytes() + bytes(_background(self.Background)), dev)
+
+    def Move(self, centers, radii=None, device: int = 0) -> bool:
+        """New centres ((n, 3)) and, unless None, radii ((n,)) for the scene's spheres, in list
+        order: sets Center and Radius on Objects and, when the scene has an up-to-date copy on
+        `device`, moves that copy's spheres in place and refits its BVH there
+        (include/tray_scene_update.h) instead of uploading again, so the next query or render
+        reuses it. Returns whether that happened: False when there was no such copy, or when the
+        update was refused (a sphere left the uploaded scene's bound, or is NaN or infinite on a
+        scene with a tree); the copy is then released and the next use uploads afresh. Either way
+        the results are those of a new Scene with the same spheres. No Go counterpart."""
+        c = np.asarray(centers, dtype=np.float64)
+        n = len(self.Objects)
+        if c.shape != (n, 3):
+            raise ValueError(f"centers must be ({n}, 3); got {c.shape}")
+        have = self._uploaded.get(device)
+        if have is not None and have[0] != self.to_array().tobytes() + bytes(_background(self.Background)):
+            have[1].release()  # stale already: something else changed since the upload
+            self._adopt(device, None)
+            have = None
+        geometry = self._geometry()
+        geometry[:, :3] = c
+        if radii is not None:
+            r = np.asarray(radii, dtype=np.float64)
+            if r.shape != (n,):
+                raise ValueError(f"radii must be ({n},); got {r.shape}")
+            geometry[:, 3] = r
+        self._set_geometry(geometry)
+        if have is None:
+            return False
+        if n == 0:  # nothing to move
+            return True
+        if have[1].update(geometry).applied:
+            self._adopt(device, have[1])
+            return True
+        have[1].release()
+        self._adopt(device, None)
+        return False
+
     def Hit(self, origins, directions, interval=(1e-6, math.inf), device: int = 0) -> np.ndarray:  # ray/objects.go:37-46
         """Scene.Hit for n rays ((n, 3) origins and directions) over Interval{1e-6,
         interval[1]}: a _lib.HIT_DTYPE array (index -1: no hit). The interval
@@ -355,6 +410,19 @@ def Orbit(camera: Camera, degrees: float) -> Camera:
 
 ORBIT_STEP_DEGREES = 1.0  # the CLI's default -orbit-step (tools/temporal_sweep.py)
 REFILL_DEFAULT = 3  # the CLI's -refill without a number (tools/temporal_variance_sweep.py)
+BOUNCE_STEP = 0.4  # the CLI's -bounce: radians of every sphere's phase between frames
+
+
+def Bounce(scene: Scene, frames: int, step: float = BOUNCE_STEP) -> np.ndarray:
+    """The geometries of `frames` frames for Tracer.RenderAnimation, (frames, n, 4) float64: the
+    spheres of `scene` with a radius below 0.5 hop above the ground, y = R + |sin(i + step x frame)|
+    for the sphere at list index i; everything else stays where it is."""
+    g = scene._geometry()
+    out = np.repeat(g[None], int(frames), axis=0)
+    small = np.nonzero(g[:, 3] < 0.5)[0]
+    for k in range(int(frames)):
+        out[k, small, 1] = g[small, 3] + np.abs(np.sin(small + step * k))
+    return out
 
 # --------------------------------------------------------------------- tracer
 _CAMERA_FIELDS = ("Position", "LookAt", "Up", "VerticalFoV", "FocalLength", "FocusDistance", "Aperture")
@@ -965,6 +1033,81 @@ class Tracer:  # ray/tracer.go:25-36
         rec = records.cpu().numpy()
         self.fresh = [int(r[0]) for r in rec]
         self.mean_age = [float(r[1]) / (h * w) for r in rec]
+        frames = [f.copy() for f in rgba.cpu().numpy()]
+        self.imageData[:] = frames[-1]
+        return frames
+
+    def RenderAnimation(self, scene: Scene | None, geometries, denoise: bool = False) -> list:
+        """Moving spheres under the tracer's camera (include/tray_scene_update.h): frame k shows the
+        scene with its spheres at geometries[k], a (k, n, 4) float64 array or device tensor of
+        {cx, cy, cz, radius} per sphere in list order, as progressive pass k of the tracer's one
+        seed. The scene is uploaded once; each frame is tray_scene_update_async, tray_render_async,
+        with denoise=True the feature buffers and the guided filter (tray_render_aov_async,
+        tray_denoise_async), and the sRGB encoding, all enqueued on one stream; nothing is read back
+        before the last frame is enqueued. A device tensor is used where it is: no copy to the host.
+
+        `applied` lists each frame's record: 1 where the spheres were moved in place, 0 where the
+        update was refused (a sphere left the bound of the scene as uploaded, section 2 of the
+        header). The records are read with the frames, so a refusal is found late: that frame is
+        then made by a release and a fresh upload of its geometry, and the frames after it again by
+        updates of the new copy. Every frame has the bits of a fresh upload's render either way.
+
+        Returns the list of (H, W, 4) uint8 RGBA frames and keeps the last in imageData and, before
+        the encoding, in `linear`; the scene's Objects end at the last geometry. ValueError for an
+        empty sequence or a shape other than (k, n, 4), before any device work. No Go counterpart."""
+        scene = self._apply_defaults(scene)
+        self.Camera.Initialize(self.width, self.height)
+        import torch
+
+        n, h, w = len(scene.Objects), self.height, self.width
+        on_device = torch.is_tensor(geometries)
+        if not on_device:
+            geometries = np.ascontiguousarray(geometries, dtype=np.float64)
+        if geometries.ndim != 3 or tuple(geometries.shape[1:]) != (n, 4) or geometries.shape[0] < 1:
+            raise ValueError(f"geometries must be (k, {n}, 4) with k >= 1; got {tuple(geometries.shape)}")
+        if on_device and geometries.dtype != torch.float64:
+            raise ValueError("geometries must be float64")
+        count = int(geometries.shape[0])
+        self.seed = self._seed()  # once: every frame is a pass of this stream
+        self.applied = []
+        if h * w == 0:
+            return [self.imageData.copy() for _ in range(count)]
+        torch, device, where, stream = self._target()
+        geo = geometries.to(where).contiguous() if on_device else torch.from_numpy(geometries).to(where)
+        dev = scene._device_scene(device)
+        records = torch.zeros((count, _lib.SCENE_UPDATE_RECORD_DTYPE.itemsize // 8), dtype=torch.float64, device=where)
+        rgba = torch.empty((count, h, w, 4), dtype=torch.uint8, device=where)
+        colour = torch.empty((h, w, 3), dtype=torch.float64, device=where)
+        aov = self._guide_buffers(torch, where) if denoise else None
+        start, uploaded = 0, False  # uploaded: frame `start` is the geometry of a fresh upload
+        while start < count:
+            for k in range(start, count):
+                if n and not (uploaded and k == start):
+                    dev.update_async(geo[k].data_ptr(), n, records[k].data_ptr(), stream)
+                params = self._params(self.seed, k)
+                dev.render_async(self.Camera._state, params, colour.data_ptr(), None, stream)
+                shown = colour
+                if denoise:
+                    dev.render_aov_async(self.Camera._state, params, *_guide_ptrs(aov), stream=stream)
+                    shown = self._denoise_device(torch, colour, aov, {})
+                _lib.linear_to_srgba_async(shown.data_ptr(), h * w, rgba[k].data_ptr(), device, stream)
+            flags = records.cpu().numpy().reshape(-1).view(_lib.SCENE_UPDATE_RECORD_DTYPE)["applied"]
+            flags = [1 if n == 0 else int(f) for f in flags[start:]]
+            if uploaded:
+                flags[0] = 0
+            refused = [i for i, f in enumerate(flags) if not f and not (uploaded and i == 0)]
+            good = refused[0] if refused else len(flags)
+            self.applied += flags[:good]
+            if not refused:
+                break
+            start, uploaded = start + good, True  # this frame and the ones after it: again, from a fresh upload
+            scene._set_geometry(geo[start].cpu().numpy())
+            dev.release()
+            scene._adopt(device, None)
+            dev = scene._device_scene(device)
+        self.linear[:] = shown.cpu().numpy()
+        scene._set_geometry(geo[count - 1].cpu().numpy())
+        scene._adopt(device, dev)
         frames = [f.copy() for f in rgba.cpu().numpy()]
         self.imageData[:] = frames[-1]
         return frames
