@@ -2,7 +2,9 @@
 
 Layout:
   csrc/          gfx950 megakernel (tray_kernel.hip), the device functions it shares
-                 with the other kernels (tray_device.hpp), C-ABI glue (tray_abi.hip),
+                 with the other kernels (tray_device.hpp), the scene and the renders of
+                 include/tray.h (tray_abi.hip; tray_scene.hpp for the other units), one unit
+                 per further header with its kernels and entry points (tray_query.hip, ...),
                  host setup (tray_host.cpp); built into libtray_amd.so
   _lib.py        ctypes binding of include/tray.h (no fallback path)
   ray.py         mirror of the Go `ray` package API (New/Render/RenderLines/...)

@@ -4,6 +4,11 @@
 // scene flattening + upload, one kernel launch per row set, copy-out. The Go
 // host's defaulting (ray/tracer.go:50-84) happens BEFORE these calls, in the
 // caller (tray_amd/ray.py or a cgo shim), exactly as Render does it.
+//
+// Holds the scene (upload, release, launch contexts), the renders, the debug knobs and
+// the definitions behind tray_scene.hpp. The entry points of the other public headers
+// live beside their kernels (tray_query.hip, tray_adaptive.hip, tray_temporal.hip,
+// tray_scene_update.hip, ...) and reach the scene through tray_scene.hpp.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,15 +25,12 @@
 #include <vector>
 
 #include "../../include/tray.h"
-#include "../../include/tray_adaptive.h"
 #include "../../include/tray_debug.h"
 #include "tray_check.hpp"
 #include "bvh.hpp"
 #include "rng.hpp"
 #include "tray_kernel.hpp"
-#include "tray_query.hpp"
-#include "tray_query_device.hpp"  // query_takes_tree, for tray_debug_query_traversal
-#include "tray_scene_update.hpp"
+#include "tray_scene.hpp"
 
 namespace tray {
 
@@ -58,15 +60,9 @@ static int knob_index(const char* name) {
     return -1;
 }
 
-static int hip_fail(hipError_t e, const char* what) {
+int hip_fail(hipError_t e, const char* what) {
     return fail(TRAY_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
-
-#define TRAY_HIP(call)                                  \
-    do {                                                \
-        hipError_t e_ = (call);                         \
-        if (e_ != hipSuccess) return hip_fail(e_, #call); \
-    } while (0)
 
 // One render slot of a device for the synchronous entry points: a stream, the
 // output workspaces, and the last scene the slot uploaded (reused while the
@@ -175,94 +171,9 @@ int device_usable(int32_t device) {
 
 }  // namespace tray
 
-// What a primary-ray candidate list depends on (compared byte for byte).
-struct CandKey {
-    tray_camera cam;
-    double ray_radius;
-    int32_t width, height, y_start, rows, tile_rows, tile_count, tile_index, multi_sample;
-};
-
-// The mutable device state ONE render uses while it runs: the work-queue word
-// (zero between launches: zeroed at allocation, then by each band's resolve
-// pass), the per-sample buffer or chunk records of a launch band, the primary-ray
-// candidate records of the last camera and row set it rendered, and the
-// traversal-stack overflow area (deep BVHs). `done` is recorded on the render's
-// stream after each launch that used it. A scene holds a few of these, so that
-// renders of one scene on different streams (or threads) run concurrently
-// without sharing any of it, as several goroutines may Render one read-only
-// *Scene at once (ray/tracer.go:48, ray/objects.go:37-46).
-struct LaunchCtx {
-    uint32_t* queue = nullptr;
-    double* samples = nullptr;
-    size_t samples_bytes = 0;
-    uint4* cand = nullptr;
-    size_t cand_bytes = 0;
-    bool cand_valid = false;
-    CandKey cand_key;
-    uint32_t* stack_ovf = nullptr;
-    size_t ovf_bytes = 0;
-    // Work order (launch_render): per 8x8 tile of the rows, the Scene.Hit calls a
-    // counting launch measured and the order the next launches hand tiles out in,
-    // valid for `order_key` (camera, rows, tiling, rays per pixel, depth).
-    uint32_t* tile_cost = nullptr;
-    size_t tile_cost_bytes = 0;
-    uint32_t* tile_order = nullptr;
-    size_t tile_order_bytes = 0;
-    bool order_valid = false;
-    CandKey order_key;
-    int32_t order_spp = 0, order_depth = 0;
-    hipEvent_t done = nullptr;
-    bool launched = false;          // `done` has been recorded
-    hipStream_t last_stream = nullptr;
-    uint64_t last_use = 0;          // the scene's launch count at its last launch
-};
-
-// Launch contexts per scene: renders beyond this many in flight at once wait
-// (on the device, hipStreamWaitEvent) for the least recently used one.
+// Launch contexts per scene (LaunchCtx, tray_scene.hpp): renders beyond this many in flight
+// at once wait (on the device, hipStreamWaitEvent) for the least recently used one.
 constexpr int kSceneContexts = 4;
-
-// A scene resident on one device. Its arrays are read-only after the upload, but
-// for tray_scene_update_async (include/tray_scene_update.h), which rewrites the
-// centres, radii and boxes in stream order; everything a render writes lives in a
-// launch context (above), taken under the scene's mutex for the time it takes to
-// enqueue the render.
-struct tray_scene_s {
-    int32_t device;
-    int32_t n;
-    int32_t n_pad;
-    double4* geo;  // n_pad entries, NaN-padded (see tray::KernelParams::geo)
-    tray::MatRec* mat;
-    tray::V3 bg_a, bg_b;
-    double max_att;  // max(1, |albedo| of every Lambertian/Metal sphere): bounds a path's throughput
-                     // (infinite when one of them is infinite or NaN: KernelParams::wild_att)
-    // exact-culling BVH (absent for tiny scenes, for scenes with a NaN or infinite
-    // coordinate or radius and for scenes that reach beyond +-kBvhMaxBound, bvh.hpp:
-    // those take the linear scan, and with no tree there are no candidate lists)
-    bool has_bvh;
-    double bvh_bound;
-    int32_t n_nodes, n_slots, n_leaves, stack_cap, leaf_max, n_global;
-    tray::Bvh4Node* nodes;
-    int32_t* leaves;
-    size_t ovf_bytes;  // traversal-stack overflow area a render needs (deep BVHs only; per context)
-    double4* bgeo;
-    int32_t* bidx;
-    tray::MatRec* bmat;
-    // One device allocation holds geo, mat, srgb and the BVH arrays (the pointers
-    // above point into it).
-    void* arena;
-    double* srgb;  // the RGBA8 encoder table (tray::srgb_thresholds), 256 doubles
-    std::mutex mu;  // guards ctx and launches
-    std::vector<LaunchCtx*> ctx;
-    uint64_t launches;
-    // tray_scene_update_async: the child references of the nodes (host copy, n_nodes x
-    // kBvhWidth), the level schedule built from them at the first update (a device buffer
-    // of the scene's own, outside the arena) and the event recorded after the last update.
-    std::vector<uint32_t> refs;
-    uint32_t* schedule;
-    int32_t n_levels;
-    hipEvent_t updated;
-    bool update_recorded;
-};
 
 using namespace tray;
 
@@ -279,7 +190,10 @@ static int validate_spheres(const tray_sphere* s, int32_t n) {
     return TRAY_OK;
 }
 
-static int validate_params(const tray_params* p) {
+// ---- what tray_scene.hpp declares for the entry points in the other units ------------
+namespace tray {
+
+int validate_params(const tray_params* p) {
     if (!p) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params");
     if (p->width <= 0 || p->height <= 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "width/height must be > 0");
     if ((uint64_t)p->width * (uint64_t)p->height > 0xFFFFFFFFull)
@@ -302,6 +216,82 @@ static int validate_params(const tray_params* p) {
         return fail(TRAY_ERR_TOO_LARGE, "pass x rays_per_pixel exceeds the 32-bit RNG sample word");
     return TRAY_OK;
 }
+
+int validate_passes(const tray_params* p, int32_t n_passes) {
+    if (n_passes < 1) return fail(TRAY_ERR_INVALID_ARGUMENT, "n_passes must be >= 1");
+    if (((uint64_t)p->pass + (uint64_t)n_passes) * (uint64_t)p->rays_per_pixel > 0x100000000ull)
+        return fail(TRAY_ERR_TOO_LARGE, "(pass + n_passes) x rays_per_pixel exceeds the 32-bit RNG sample word");
+    return TRAY_OK;
+}
+
+bool wants_bvh(const tray_scene_s* sc, int32_t flags) { return sc->has_bvh && !(flags & TRAY_FLAG_LINEAR_SCAN); }
+
+int validate_query(tray_scene_t sc, const void* rays, int64_t n, int32_t flags, const void* out) {
+    if (n < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative ray count");
+    if (n > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 rays in one query");
+    if (flags & ~TRAY_FLAG_LINEAR_SCAN)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "unknown flags (a query takes TRAY_FLAG_LINEAR_SCAN only)");
+    if (n > 0 && !rays) return fail(TRAY_ERR_INVALID_ARGUMENT, "null ray buffer");
+    if (n > 0 && !out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null result buffer");
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    return TRAY_OK;
+}
+
+void scene_params(const tray_scene_s* sc, KernelParams& k) {
+    k.geo = sc->geo;
+    k.mat = sc->mat;
+    k.n = sc->n;
+    k.n_pad = sc->n_pad;
+    k.bg_a = sc->bg_a;
+    k.bg_b = sc->bg_b;
+    k.srgb = sc->srgb;
+    k.nodes = sc->nodes;
+    k.bgeo = sc->bgeo;
+    k.bidx = sc->bidx;
+    k.bmat = sc->bmat;
+    k.n_nodes = sc->n_nodes;
+    k.n_slots = sc->n_slots;
+    k.n_leaves = sc->n_leaves;
+    k.n_global = sc->n_global;
+    k.leaves = sc->leaves;
+    k.leaf_single = sc->leaf_max == 1 ? 1 : 0;
+    k.stack_cap = sc->stack_cap;
+    k.wild_att = std::isfinite(sc->max_att) ? 0u : 1u;
+}
+
+void camera_params(const tray_camera* cam, KernelParams& k) {
+    k.focus_time = cam->focus_distance / cam->focal_length;  // ray/camera.go:134
+    memcpy(k.cam.position, cam->position, sizeof(k.cam.position));
+    memcpy(k.cam.pixel00, cam->pixel00, sizeof(k.cam.pixel00));
+    memcpy(k.cam.pixel_x, cam->pixel_x, sizeof(k.cam.pixel_x));
+    memcpy(k.cam.pixel_y, cam->pixel_y, sizeof(k.cam.pixel_y));
+    memcpy(k.cam.defocus_u, cam->defocus_u, sizeof(k.cam.defocus_u));
+    memcpy(k.cam.defocus_v, cam->defocus_v, sizeof(k.cam.defocus_v));
+    k.cam.aperture = cam->aperture;
+}
+void key_params(uint64_t seed, KernelParams& k) {
+    const DrawKey dk = draw_key(seed);  // include/tray.h, ABI 6
+    k.key[0] = dk.k0, k.key[1] = dk.k1, k.key[2] = dk.k2, k.key[3] = dk.k3;
+}
+
+void frame_params(const tray_camera* cam, const tray_params* p, int32_t rows, int32_t n_passes, KernelParams& k) {
+    k.width = p->width;
+    k.height = p->height;
+    k.spp = p->rays_per_pixel;
+    k.max_depth = p->max_depth;
+    k.y_start = p->y_start;
+    k.rows = rows;
+    k.tile_rows = p->tile_rows;
+    k.tile_count = p->tile_rows > 0 ? p->tile_count : 1;
+    k.tile_index = p->tile_rows > 0 ? p->tile_index : 0;
+    k.ray_radius = p->ray_radius;
+    k.passes = (uint32_t)n_passes;
+    k.pass0 = (uint32_t)p->pass;
+    camera_params(cam, k);
+    key_params(p->seed, k);
+}
+
+}  // namespace tray
 
 static size_t bytes_per_pixel(int32_t fmt) {
     return fmt == TRAY_OUT_RGB_F64 ? 24 : fmt == TRAY_OUT_RGB_F32 ? 12 : 4;
@@ -365,19 +355,6 @@ int tray_debug_plain_instance(uint32_t facts, int32_t rays_per_pixel, int32_t ti
                                     acc, lds_mode)
                      ? 1
                      : 0;
-    return TRAY_OK;
-}
-
-static_assert(TRAY_QUERY_KIND_PLAIN == kQueryPlain && TRAY_QUERY_KIND_PIXELS == kQueryPixels &&
-                  TRAY_QUERY_KIND_TEMPORAL == kQueryTemporal,
-              "tray_debug.h names the kinds of tray_query_device.hpp");
-
-int tray_debug_query_traversal(int32_t kind, int32_t stack_depth, int32_t* bvh_out) {
-    if (!bvh_out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null argument");
-    if (kind < TRAY_QUERY_KIND_PLAIN || kind > TRAY_QUERY_KIND_TEMPORAL)
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "unknown query kind");
-    if (stack_depth < 0 || stack_depth > (1 << 20)) return fail(TRAY_ERR_INVALID_ARGUMENT, "stack_depth out of range");
-    *bvh_out = query_takes_tree(static_cast<QueryKind>(kind), stack_depth + kStackSlack) ? 1 : 0;
     return TRAY_OK;
 }
 
@@ -484,17 +461,9 @@ int tray_scene_upload(const tray_sphere* spheres, int32_t n, const tray_backgrou
     sc->n_nodes = (int32_t)bvh.nodes.size();
     sc->n_slots = (int32_t)bvh.geo.size();
     sc->n_leaves = (int32_t)bvh.leaves.size();
-    sc->leaves = nullptr;
-    sc->ovf_bytes = 0;
-    sc->launches = 0;
     sc->stack_cap = bvh.stack_max + kStackSlack;
     sc->leaf_max = has_bvh ? bvh.leaf_max : 0;
     sc->n_global = has_bvh ? bvh.n_global : 0;
-    sc->nodes = nullptr;
-    sc->bgeo = nullptr;
-    sc->bidx = nullptr;
-    sc->bmat = nullptr;
-    sc->srgb = nullptr;
     std::vector<MatRec> bmat(bvh.idx.size());
     for (size_t i = 0; i < bvh.idx.size(); ++i) {
         const int32_t k = bvh.idx[i];
@@ -503,10 +472,7 @@ int tray_scene_upload(const tray_sphere* spheres, int32_t n, const tray_backgrou
     }
     sc->n = n;
     sc->n_pad = n_pad;
-    sc->geo = nullptr;
-    sc->mat = nullptr;
-    sc->max_att = 1.0;
-    for (int32_t i = 0; i < n; ++i)
+    for (int32_t i = 0; i < n; ++i)  // max_att starts at 1
         if (spheres[i].material != TRAY_DIELECTRIC)  // Dielectric attenuates by exactly 1
             for (int c = 0; c < 3; ++c) {
                 const double a = std::fabs(spheres[i].albedo[c]);
@@ -543,7 +509,6 @@ int tray_scene_upload(const tray_sphere* spheres, int32_t n, const tray_backgrou
         if (q.src && q.bytes) memcpy(image.data() + at, q.src, q.bytes);
         at += (q.bytes + kAlign - 1) / kAlign * kAlign;
     }
-    sc->arena = nullptr;
     hipError_t e = hipMalloc(&sc->arena, total);
     if (e == hipSuccess) e = hipMemcpy(sc->arena, image.data(), total, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
@@ -551,10 +516,6 @@ int tray_scene_upload(const tray_sphere* spheres, int32_t n, const tray_backgrou
             *parts[i].dst = parts[i].bytes ? static_cast<uint8_t*>(sc->arena) + offsets[i] : nullptr;
     }
     if (has_bvh) sc->ovf_bytes = bvh_stack_overflow_bytes(bvh.stack_max + kStackSlack, device);
-    sc->schedule = nullptr;
-    sc->n_levels = 0;
-    sc->updated = nullptr;
-    sc->update_recorded = false;
     if (has_bvh) {
         sc->refs.reserve(bvh.nodes.size() * kBvhWidth);
         for (const Bvh4Node& node : bvh.nodes) sc->refs.insert(sc->refs.end(), node.ref, node.ref + kBvhWidth);
@@ -649,78 +610,6 @@ static int32_t fixed_point_shift(const tray_scene_s* sc, const tray_params* p) {
     if (p->rays_per_pixel > (1 << 15)) return 0;  // the pixel's total r x 2^47 must stay below 2^63
     const int32_t k = kAccBits - e;
     return k >= kAccMinShift ? std::min(k, 600) : 0;
-}
-
-// The scene's arrays and background in the kernel parameters (renders and ray queries).
-static void scene_params(const tray_scene_s* sc, KernelParams& k) {
-    k.geo = sc->geo;
-    k.mat = sc->mat;
-    k.n = sc->n;
-    k.n_pad = sc->n_pad;
-    k.bg_a = sc->bg_a;
-    k.bg_b = sc->bg_b;
-    k.srgb = sc->srgb;
-    k.nodes = sc->nodes;
-    k.bgeo = sc->bgeo;
-    k.bidx = sc->bidx;
-    k.bmat = sc->bmat;
-    k.n_nodes = sc->n_nodes;
-    k.n_slots = sc->n_slots;
-    k.n_leaves = sc->n_leaves;
-    k.n_global = sc->n_global;
-    k.leaves = sc->leaves;
-    k.leaf_single = sc->leaf_max == 1 ? 1 : 0;
-    k.stack_cap = sc->stack_cap;
-    k.wild_att = std::isfinite(sc->max_att) ? 0u : 1u;
-}
-
-// The camera and the draw key of `seed` in the kernel parameters (get_ray, draw).
-static void camera_params(const tray_camera* cam, KernelParams& k) {
-    k.focus_time = cam->focus_distance / cam->focal_length;  // ray/camera.go:134
-    memcpy(k.cam.position, cam->position, sizeof(k.cam.position));
-    memcpy(k.cam.pixel00, cam->pixel00, sizeof(k.cam.pixel00));
-    memcpy(k.cam.pixel_x, cam->pixel_x, sizeof(k.cam.pixel_x));
-    memcpy(k.cam.pixel_y, cam->pixel_y, sizeof(k.cam.pixel_y));
-    memcpy(k.cam.defocus_u, cam->defocus_u, sizeof(k.cam.defocus_u));
-    memcpy(k.cam.defocus_v, cam->defocus_v, sizeof(k.cam.defocus_v));
-    k.cam.aperture = cam->aperture;
-}
-static void key_params(uint64_t seed, KernelParams& k) {
-    const DrawKey dk = draw_key(seed);  // include/tray.h, ABI 6
-    k.key[0] = dk.k0, k.key[1] = dk.k1, k.key[2] = dk.k2, k.key[3] = dk.k3;
-}
-
-// The image, row-set, pass, camera and draw-key fields of the kernel parameters: `n_passes`
-// passes, from p->pass on, of the `rows` = tray_params_rows(p) rows of p's row set.
-static void frame_params(const tray_camera* cam, const tray_params* p, int32_t rows, int32_t n_passes,
-                         KernelParams& k) {
-    k.width = p->width;
-    k.height = p->height;
-    k.spp = p->rays_per_pixel;
-    k.max_depth = p->max_depth;
-    k.y_start = p->y_start;
-    k.rows = rows;
-    k.tile_rows = p->tile_rows;
-    k.tile_count = p->tile_rows > 0 ? p->tile_count : 1;
-    k.tile_index = p->tile_rows > 0 ? p->tile_index : 0;
-    k.ray_radius = p->ray_radius;
-    k.passes = (uint32_t)n_passes;
-    k.pass0 = (uint32_t)p->pass;
-    camera_params(cam, k);
-    key_params(p->seed, k);
-}
-
-// n_passes passes from p->pass on (p validated): at least one, and their sample words fit 32 bits.
-static int validate_passes(const tray_params* p, int32_t n_passes) {
-    if (n_passes < 1) return fail(TRAY_ERR_INVALID_ARGUMENT, "n_passes must be >= 1");
-    if (((uint64_t)p->pass + (uint64_t)n_passes) * (uint64_t)p->rays_per_pixel > 0x100000000ull)
-        return fail(TRAY_ERR_TOO_LARGE, "(pass + n_passes) x rays_per_pixel exceeds the 32-bit RNG sample word");
-    return TRAY_OK;
-}
-
-// The caller's choice between the scene's BVH and the reference-order linear scan.
-static bool wants_bvh(const tray_scene_s* sc, int32_t flags) {
-    return sc->has_bvh && !(flags & TRAY_FLAG_LINEAR_SCAN);
 }
 
 // The kernel parameters of a render of `p` on `sc` (everything but the output,
@@ -975,412 +864,6 @@ int tray_render_stats_async(tray_scene_t sc, const tray_camera* cam, const tray_
     q.output = TRAY_OUT_RGB_F32;
     return render_async_impl(sc, cam, &q, out_device, nullptr, reinterpret_cast<unsigned long long*>(stats_device),
                              stream);
-}
-
-// ---- ray queries (include/tray_query.h) ----------------------------------------
-int32_t tray_query_version(void) { return TRAY_QUERY_VERSION; }
-
-constexpr int64_t kQueryMaxRays = kMaxPixels;  // ray indices are 32-bit on the device
-
-// The checks the scene queries share, before any device work.
-static int validate_query(tray_scene_t sc, const void* rays, int64_t n, int32_t flags, const void* out) {
-    if (n < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative ray count");
-    if (n > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 rays in one query");
-    if (flags & ~TRAY_FLAG_LINEAR_SCAN)
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "unknown flags (a query takes TRAY_FLAG_LINEAR_SCAN only)");
-    if (n > 0 && !rays) return fail(TRAY_ERR_INVALID_ARGUMENT, "null ray buffer");
-    if (n > 0 && !out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null result buffer");
-    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
-    return TRAY_OK;
-}
-
-int tray_camera_rays_async(const tray_camera* cam, const tray_params* p, int32_t device, tray_ray* rays_device,
-                           uint32_t* ids_device, void* stream) {
-    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
-    int rc = validate_params(p);
-    if (rc) return rc;
-    const int64_t rows = tray_params_rows(p);
-    if (rows * (int64_t)p->width > kQueryMaxRays / p->rays_per_pixel)
-        return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 camera rays in one query");
-    const int64_t n = rows * (int64_t)p->width * (int64_t)p->rays_per_pixel;
-    if (n > 0 && !rays_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null ray buffer");
-    if (n == 0) return TRAY_OK;
-    rc = device_usable(device);
-    if (rc) return rc;
-    KernelParams k;
-    memset(&k, 0, sizeof(k));
-    frame_params(cam, p, (int32_t)rows, 1, k);
-    TRAY_HIP(hipSetDevice(device));
-    TRAY_HIP(launch_camera_rays(k, rays_device, ids_device, (uint32_t)n, static_cast<hipStream_t>(stream)));
-    return TRAY_OK;
-}
-
-int tray_scene_hit_async(tray_scene_t sc, const tray_ray* rays_device, int64_t n, double t_end, int32_t flags,
-                         tray_hit* hits_device, void* stream) {
-    if (t_end != t_end) return fail(TRAY_ERR_INVALID_ARGUMENT, "t_end is NaN");
-    int rc = validate_query(sc, rays_device, n, flags, hits_device);
-    if (rc) return rc;
-    if (n == 0) return TRAY_OK;
-    KernelParams k;
-    memset(&k, 0, sizeof(k));
-    scene_params(sc, k);
-    TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_scene_hit(k, wants_bvh(sc, flags), sc->bvh_bound, rays_device, (uint32_t)n, t_end, hits_device,
-                              static_cast<hipStream_t>(stream)));
-    return TRAY_OK;
-}
-
-int tray_ray_color_async(tray_scene_t sc, const tray_ray* rays_device, const uint32_t* ids_device, int64_t n,
-                         int32_t max_depth, uint64_t seed, int32_t flags, double* rgb_device,
-                         uint32_t* segments_device, void* stream) {
-    if (max_depth <= 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "max_depth must be > 0");
-    int rc = validate_query(sc, rays_device, n, flags, rgb_device);
-    if (rc) return rc;
-    if (n == 0) return TRAY_OK;
-    KernelParams k;
-    memset(&k, 0, sizeof(k));
-    scene_params(sc, k);
-    key_params(seed, k);
-    k.max_depth = max_depth;
-    TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_ray_color(k, wants_bvh(sc, flags), sc->bvh_bound, rays_device, ids_device, (uint32_t)n, rgb_device,
-                              segments_device, static_cast<hipStream_t>(stream)));
-    return TRAY_OK;
-}
-
-// ---- scatter, sky and occlusion queries (include/tray_shade.h) -------------------
-int32_t tray_shade_version(void) { return TRAY_SHADE_VERSION; }
-
-int tray_scatter_async(tray_scene_t sc, const tray_ray* rays_device, const tray_hit* hits_device,
-                       const uint32_t* ids_device, int64_t n, uint32_t bounce, uint64_t seed,
-                       tray_scatter* out_device, void* stream) {
-    int rc = validate_query(sc, rays_device, n, 0, out_device);
-    if (rc) return rc;
-    if (n > 0 && !hits_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null hit buffer");
-    if (n == 0) return TRAY_OK;
-    KernelParams k;
-    memset(&k, 0, sizeof(k));
-    scene_params(sc, k);
-    key_params(seed, k);
-    TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_scatter(k, rays_device, hits_device, ids_device, (uint32_t)n, bounce, out_device,
-                            static_cast<hipStream_t>(stream)));
-    return TRAY_OK;
-}
-
-int tray_background_hit_async(const tray_background* bg, const tray_ray* rays_device, int64_t n, double* rgb_device,
-                              int32_t device, void* stream) {
-    if (n < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative ray count");
-    if (n > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 rays in one query");
-    if (n > 0 && !rays_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null ray buffer");
-    if (n > 0 && !rgb_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null result buffer");
-    if (!bg) return fail(TRAY_ERR_INVALID_ARGUMENT, "null background");
-    if (n == 0) return TRAY_OK;
-    const int rc = device_usable(device);
-    if (rc) return rc;
-    TRAY_HIP(hipSetDevice(device));
-    TRAY_HIP(launch_background_hit(V3{bg->color_a[0], bg->color_a[1], bg->color_a[2]},
-                                   V3{bg->color_b[0], bg->color_b[1], bg->color_b[2]}, rays_device, (uint32_t)n,
-                                   rgb_device, static_cast<hipStream_t>(stream)));
-    return TRAY_OK;
-}
-
-int tray_scene_occluded_async(tray_scene_t sc, const tray_ray* rays_device, const double* t_end_device, int64_t n,
-                              double t_end, int32_t flags, uint8_t* occluded_device, void* stream) {
-    if (t_end != t_end) return fail(TRAY_ERR_INVALID_ARGUMENT, "t_end is NaN");
-    int rc = validate_query(sc, rays_device, n, flags, occluded_device);
-    if (rc) return rc;
-    if (n == 0) return TRAY_OK;
-    KernelParams k;
-    memset(&k, 0, sizeof(k));
-    scene_params(sc, k);
-    TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_scene_occluded(k, wants_bvh(sc, flags), sc->bvh_bound, rays_device, t_end_device, (uint32_t)n,
-                                   t_end, occluded_device, static_cast<hipStream_t>(stream)));
-    return TRAY_OK;
-}
-
-// ---- first-hit feature buffers (include/tray_aov.h) -----------------------------
-int32_t tray_aov_version(void) { return TRAY_AOV_VERSION; }
-
-int tray_render_aov_async(tray_scene_t sc, const tray_camera* cam, const tray_params* p, const tray_aov_buffers* out,
-                          void* stream) {
-    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
-    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
-    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null feature buffers (out)");
-    int rc = validate_params(p);
-    if (rc) return rc;
-    if (!out->albedo && !out->normal && !out->depth && !out->coverage && !out->index)
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "every feature buffer is null: nothing to write");
-    const int64_t rows = tray_params_rows(p);
-    if (rows * (int64_t)p->width > kQueryMaxRays)
-        return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one feature-buffer call");
-    if (rows == 0) return TRAY_OK;
-    // One lane per pixel and a loop over its samples: rows x width x rays_per_pixel has no
-    // limit here (the megakernel's 8-row band limit, band_fits, is about its item indices).
-    KernelParams k;
-    memset(&k, 0, sizeof(k));
-    scene_params(sc, k);
-    frame_params(cam, p, (int32_t)rows, 1, k);
-    TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_render_aov(k, wants_bvh(sc, p->flags), sc->bvh_bound, *out, static_cast<hipStream_t>(stream)));
-    return TRAY_OK;
-}
-
-// ---- the renderer over a pixel list (include/tray_adaptive.h, section 2) ---------
-int tray_render_pixels_async(tray_scene_t sc, const tray_camera* cam, const tray_params* p,
-                             const uint32_t* pixels_device, int64_t n_pixels, const int32_t* pass_plane_device,
-                             int32_t n_passes, double* out_device, uint32_t* segments_device, void* stream) {
-    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
-    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
-    int rc = validate_params(p);
-    if (rc) return rc;
-    if (p->output != TRAY_OUT_RGB_F64)
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "a pixel list renders TRAY_OUT_RGB_F64 only");
-    if (n_pixels < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative n_pixels");
-    rc = validate_passes(p, n_passes);
-    if (rc) return rc;
-    const int64_t rows = tray_params_rows(p);
-    if (rows * (int64_t)p->width > kQueryMaxRays)
-        return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one row set");
-    // n_pixels x n_passes x r <= 2^31 - 1, without overflow: each factor is below 2^63 / 2^31.
-    if (n_pixels > kQueryMaxRays || n_pixels * (int64_t)n_passes > kQueryMaxRays ||
-        n_pixels * (int64_t)n_passes > kQueryMaxRays / p->rays_per_pixel)
-        return fail(TRAY_ERR_TOO_LARGE, "n_pixels x n_passes x rays_per_pixel exceeds 2^31 - 1");
-    if (n_pixels == 0) return TRAY_OK;
-    if (!pixels_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null pixel list");
-    if (!out_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null result buffer");
-    KernelParams k;
-    memset(&k, 0, sizeof(k));
-    scene_params(sc, k);
-    frame_params(cam, p, (int32_t)rows, n_passes, k);
-    TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_render_pixels(k, wants_bvh(sc, p->flags), sc->bvh_bound, pixels_device, (uint32_t)n_pixels,
-                                  pass_plane_device, (uint32_t)n_passes, out_device, segments_device,
-                                  static_cast<hipStream_t>(stream)));
-    return TRAY_OK;
-}
-
-// ---- temporal reprojection (include/tray_temporal.h) -----------------------------
-int32_t tray_temporal_version(void) { return TRAY_TEMPORAL_VERSION; }
-
-int tray_temporal_default_params(tray_temporal_params* out) {
-    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params (out)");
-    out->max_history = 32;       // tools/temporal_sweep.py, DESIGN.md 8q
-    out->flags = 0;
-    out->depth_tolerance = 0.1;  // the same sweep
-    out->snap = 0x1.0p-20;
-    out->reserved = 0;
-    return TRAY_OK;
-}
-
-// Both steps (the plain one without the M2 and variance rows): the states come as
-// tray_temporal_var_state, a plain state widened with a null m2.
-static int temporal_step(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
-                         const tray_temporal_params* tp, const double* frame_device,
-                         const tray_temporal_var_state* history, const tray_temporal_var_state* out, bool with_m2,
-                         double* variance_device, tray_temporal_record* record_device, void* stream) {
-    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
-    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
-    if (!tp) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params");
-    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null state (out)");
-    if ((history == nullptr) != (prev == nullptr))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "history and prev_camera must both be given or both be null");
-    if (out->width < 0 || out->height < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative width or height");
-    if (history && (history->width != out->width || history->height != out->height))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "history and out differ in width or height");
-    if (tp->max_history < 1 || tp->max_history > (1 << 30))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "max_history must be in 1 .. 2^30");
-    if (tp->flags & ~TRAY_FLAG_LINEAR_SCAN)
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "unknown flags (only TRAY_FLAG_LINEAR_SCAN applies)");
-    if (!(std::isfinite(tp->depth_tolerance) && tp->depth_tolerance >= 0.0))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "depth_tolerance must be finite and >= 0");
-    if (!(std::isfinite(tp->snap) && tp->snap >= 0.0 && tp->snap < 0.5))
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "snap must be finite, >= 0 and < 0.5");
-    if (tp->reserved != 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "reserved must be 0");
-    const int64_t image = (int64_t)out->width * (int64_t)out->height;
-    if (image > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
-    if (image == 0) return TRAY_OK;
-    // The spans: outputs first (the first n_out; the variance and the record nullable), then what is only read.
-    const size_t px = (size_t)image;
-    Span spans[13];
-    int n = 0;
-    uint32_t nullable = 0;
-    spans[n++] = {out->colour, px * 24, 8, "out.colour"};
-    if (with_m2) spans[n++] = {out->m2, px * 24, 8, "out.m2"};
-    spans[n++] = {out->age, px * 4, 4, "out.age"};
-    spans[n++] = {out->index, px * 4, 4, "out.index"};
-    spans[n++] = {out->depth, px * 8, 8, "out.depth"};
-    if (with_m2) {
-        nullable |= 1u << n;
-        spans[n++] = {variance_device, px * 24, 8, "the variance"};
-    }
-    nullable |= 1u << n;
-    spans[n++] = {record_device, sizeof(tray_temporal_record), 8, "the record"};
-    const int n_out = n;
-    spans[n++] = {frame_device, px * 24, 8, "the frame"};
-    if (history) {
-        spans[n++] = {history->colour, px * 24, 8, "history.colour"};
-        if (with_m2) spans[n++] = {history->m2, px * 24, 8, "history.m2"};
-        spans[n++] = {history->age, px * 4, 4, "history.age"};
-        spans[n++] = {history->index, px * 4, 4, "history.index"};
-        spans[n++] = {history->depth, px * 8, 8, "history.depth"};
-    }
-    int rc = check_nulls(spans, n, nullable);
-    if (!rc) rc = check_alignment(spans, n);
-    if (!rc) rc = check_overlaps(spans, n, n_out);
-    if (rc) return rc;
-    KernelParams k;
-    memset(&k, 0, sizeof(k));
-    scene_params(sc, k);
-    camera_params(cam, k);
-    k.width = out->width;
-    k.height = out->height;
-    k.rows = out->height;
-    TRAY_HIP(hipSetDevice(sc->device));
-    TRAY_HIP(launch_temporal_step(k, wants_bvh(sc, tp->flags), sc->bvh_bound, prev, *tp, frame_device, history, *out,
-                                  variance_device, record_device, static_cast<hipStream_t>(stream)));
-    return TRAY_OK;
-}
-
-static tray_temporal_var_state without_m2(const tray_temporal_state& s) {
-    return tray_temporal_var_state{s.colour, nullptr, s.age, s.index, s.depth, s.width, s.height};
-}
-
-int tray_temporal_step_async(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
-                             const tray_temporal_params* tp, const double* frame_device,
-                             const tray_temporal_state* history, const tray_temporal_state* out,
-                             tray_temporal_record* record_device, void* stream) {
-    tray_temporal_var_state h{}, o{};
-    if (history) h = without_m2(*history);
-    if (out) o = without_m2(*out);
-    return temporal_step(sc, cam, prev, tp, frame_device, history ? &h : nullptr, out ? &o : nullptr, false, nullptr,
-                         record_device, stream);
-}
-
-// ---- temporal reprojection with M2 (include/tray_temporal_variance.h) --------------
-int32_t tray_temporal_var_version(void) { return TRAY_TEMPORAL_VAR_VERSION; }
-
-int tray_temporal_var_step_async(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
-                                 const tray_temporal_params* tp, const double* frame_device,
-                                 const tray_temporal_var_state* history, const tray_temporal_var_state* out,
-                                 double* variance_device, tray_temporal_record* record_device, void* stream) {
-    return temporal_step(sc, cam, prev, tp, frame_device, history, out, true, variance_device, record_device, stream);
-}
-
-int tray_temporal_var_variance_async(const tray_temporal_var_state* state, const uint32_t* pixels_device,
-                                     int64_t n_pixels, double* variance_device, int32_t device, void* stream) {
-    if (!state) return fail(TRAY_ERR_INVALID_ARGUMENT, "null state");
-    if (state->width < 0 || state->height < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative width or height");
-    if (pixels_device && n_pixels < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative n_pixels");
-    const int64_t image = (int64_t)state->width * (int64_t)state->height;
-    if (image > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
-    if (pixels_device && n_pixels > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "n_pixels exceeds 2^31 - 1");
-    if (image == 0 || (pixels_device && n_pixels == 0)) return TRAY_OK;
-    const size_t px = (size_t)image;
-    const Span spans[4] = {{variance_device, px * 24, 8, "the variance"},
-                           {state->m2, px * 24, 8, "m2"},
-                           {state->age, px * 4, 4, "age"},
-                           {pixels_device, pixels_device ? (size_t)n_pixels * 4 : 0, 4, "the pixel list"}};
-    int rc = check_nulls(spans, 4, 1u << 3);
-    if (!rc) rc = check_alignment(spans, 4);
-    if (!rc) rc = check_overlaps(spans, 4, 1);
-    if (!rc) rc = device_usable(device);
-    if (rc) return rc;
-    TRAY_HIP(hipSetDevice(device));
-    TRAY_HIP(launch_temporal_variance(state->m2, state->age, (uint32_t)image, pixels_device,
-                                      pixels_device ? (uint32_t)n_pixels : 0u, variance_device,
-                                      static_cast<hipStream_t>(stream)));
-    return TRAY_OK;
-}
-
-// ---- moving spheres (include/tray_scene_update.h) ---------------------------------
-int tray_scene_update_async(tray_scene_t sc, const double* geometry_device, int32_t n_spheres,
-                            tray_scene_update_record* record_device, void* stream_arg) {
-    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
-    if (!geometry_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null geometry");
-    if (!record_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null record");
-    if (n_spheres != sc->n)
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "n_spheres is " + std::to_string(n_spheres) + ", the scene has " +
-                                                   std::to_string(sc->n) + ": an update keeps the sphere count");
-    const hipStream_t stream = static_cast<hipStream_t>(stream_arg);
-    TRAY_HIP(hipSetDevice(sc->device));
-    std::lock_guard<std::mutex> lk(sc->mu);
-    if (sc->has_bvh && !sc->schedule) {  // the first update: topology only, so built once
-        int32_t n_levels = 0;
-        const std::vector<uint32_t> sched = refit_schedule(sc->refs.data(), sc->n_nodes, &n_levels);
-        uint32_t* dev = nullptr;
-        TRAY_HIP(hipMalloc(reinterpret_cast<void**>(&dev), sched.size() * sizeof(uint32_t)));
-        const hipError_t e = hipMemcpy(dev, sched.data(), sched.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(dev);
-            return hip_fail(e, "level schedule");
-        }
-        sc->schedule = dev;
-        sc->n_levels = n_levels;
-    }
-    if (!sc->updated) TRAY_HIP(hipEventCreateWithFlags(&sc->updated, hipEventDisableTiming));
-    // Renders enqueued so far read the old geometry: the update waits for each context's last
-    // one (on the device). Their candidate lists and work orders were the old geometry's.
-    for (LaunchCtx* c : sc->ctx) {
-        if (c->launched && c->last_stream != stream) TRAY_HIP(hipStreamWaitEvent(stream, c->done, 0));
-        c->cand_valid = c->order_valid = false;
-    }
-    SceneUpdateArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = geometry_device;
-    a.n = sc->n;
-    a.geo = sc->geo;
-    a.mat = sc->mat;
-    a.has_bvh = sc->has_bvh ? 1 : 0;
-    if (sc->has_bvh) {
-        a.n_slots = sc->n_slots;
-        a.bgeo = sc->bgeo;
-        a.bmat = sc->bmat;
-        a.bidx = sc->bidx;
-        a.nodes = sc->nodes;
-        a.n_nodes = sc->n_nodes;
-        a.leaves = sc->leaves;
-        a.schedule = sc->schedule;
-        a.n_levels = sc->n_levels;
-        a.bound = sc->bvh_bound;
-        a.pad = 4e-6 * sc->bvh_bound;  // Builder::pad (tray_bvh.cpp)
-    }
-    a.record = record_device;
-    TRAY_HIP(launch_scene_update(a, stream));
-    const hipError_t e = hipEventRecord(sc->updated, stream);
-    if (e != hipSuccess) {  // nothing marks the update's end: wait for it here
-        (void)hipStreamSynchronize(stream);
-        return hip_fail(e, "hipEventRecord");
-    }
-    sc->update_recorded = true;
-    return TRAY_OK;
-}
-
-int tray_scene_update(tray_scene_t sc, const double* geometry_host, int32_t n_spheres,
-                      tray_scene_update_record* record_out) {
-    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
-    if (!geometry_host) return fail(TRAY_ERR_INVALID_ARGUMENT, "null geometry");
-    if (!record_out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null record");
-    if (n_spheres != sc->n)
-        return fail(TRAY_ERR_INVALID_ARGUMENT, "n_spheres is " + std::to_string(n_spheres) + ", the scene has " +
-                                                   std::to_string(sc->n) + ": an update keeps the sphere count");
-    TRAY_HIP(hipSetDevice(sc->device));
-    const size_t geo_bytes = sizeof(double) * 4 * (size_t)n_spheres;
-    uint8_t* staging = nullptr;  // the record, then the geometry
-    TRAY_HIP(hipMalloc(reinterpret_cast<void**>(&staging), sizeof(tray_scene_update_record) + geo_bytes + 32));
-    tray_scene_update_record* record_device = reinterpret_cast<tray_scene_update_record*>(staging);
-    double* geometry_device = reinterpret_cast<double*>(staging + sizeof(tray_scene_update_record));
-    hipError_t e = geo_bytes ? hipMemcpy(geometry_device, geometry_host, geo_bytes, hipMemcpyHostToDevice) : hipSuccess;
-    int rc = e == hipSuccess ? tray_scene_update_async(sc, geometry_device, n_spheres, record_device, nullptr)
-                             : hip_fail(e, "geometry staging");
-    if (rc == TRAY_OK) {
-        e = hipStreamSynchronize(nullptr);
-        if (e == hipSuccess) e = hipMemcpy(record_out, record_device, sizeof(*record_out), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "scene update");
-    }
-    (void)hipFree(staging);
-    return rc;
 }
 
 int tray_debug_scene_nodes(tray_scene_t sc, void* nodes_out, size_t capacity_bytes, size_t* bytes_out) {

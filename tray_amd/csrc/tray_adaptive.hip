@@ -6,8 +6,11 @@
 // tray_query_device.hpp (query_hit, query_shade with its scatter_step, the stack
 // policy, query_args) and, under that, tray_device.hpp (get_ray, camera_block, row_of,
 // kp_fresh, ...). The metric pass streams the state the way accum_fold_kernel does,
-// through tray_stream.hpp. Compiled with -ffp-contract=off like every other unit; the
-// public header is the contract.
+// through tray_stream.hpp. The header's entry points are at the end of the file; the
+// renderer's reaches its scene through tray_scene.hpp. Compiled with -ffp-contract=off
+// like every other unit; the public header is the contract.
+
+#include <string.h>
 
 #include <algorithm>
 #include <cmath>
@@ -17,6 +20,7 @@
 #include "../../include/tray_adaptive.h"
 #include "tray_check.hpp"
 #include "tray_query_device.hpp"
+#include "tray_scene.hpp"
 #include "tray_stream.hpp"
 
 namespace tray {
@@ -177,34 +181,6 @@ __global__ __launch_bounds__(kQueryBlock, 5) void render_pixels_kernel(PixelLaun
         }
         if (round + 1 < a.rounds) __syncthreads();  // the next round overwrites the parked colours
     }
-}
-
-hipError_t launch_render_pixels(KernelParams p, bool use_bvh, double bound, const uint32_t* pixels, uint32_t n_pixels,
-                                const int32_t* pass_plane, uint32_t n_passes, double* out, uint32_t* segments,
-                                hipStream_t stream) {
-    if (n_pixels == 0 || n_passes == 0) return hipSuccess;
-    p.div_tile_rows = make_fastdiv((uint32_t)std::max(p.tile_rows, 1));  // row_of
-    size_t lds = 0;
-    // Stacks that do not fit beside the parked colours: the scan (query_takes_tree).
-    const QueryArgs q = query_args(p, use_bvh, bound, nullptr, 0, lds, kQueryPixels);
-    PixelArgs a{};
-    a.pixels = pixels;
-    a.plane = pass_plane;
-    a.out = out;
-    a.segments = segments;
-    a.n_pixels = n_pixels;
-    a.n_groups = n_pixels * n_passes;  // the caller checked n_pixels x n_passes x r <= 2^31 - 1
-    a.image_pixels = (uint32_t)p.rows * (uint32_t)p.width;
-    const uint32_t r = (uint32_t)p.spp;
-    a.g = r < (uint32_t)kQueryBlock ? r : (uint32_t)kQueryBlock;
-    a.unit = a.g <= 64u ? 64u : (uint32_t)kQueryBlock;
-    a.groups_per_unit = a.unit / a.g;
-    const uint32_t groups_per_block = a.groups_per_unit * ((uint32_t)kQueryBlock / a.unit);
-    a.rounds = (r + a.g - 1u) / a.g;
-    a.inv_spp = 1.0 / (double)p.spp;
-    const uint32_t blocks = (a.n_groups + groups_per_block - 1u) / groups_per_block;
-    hipLaunchKernelGGL(render_pixels_kernel, dim3(blocks), dim3(kQueryBlock), lds, stream, PixelLaunch{p, q, a});
-    return hipGetLastError();
 }
 
 namespace {
@@ -465,6 +441,61 @@ int tray_adaptive_default_params(tray_adaptive_params* out) {
     out->max_passes = 64;
     out->dilate = 1;
     out->reserved = 0;
+    return TRAY_OK;
+}
+
+// Section 2: the ordered-sum pixel means of the listed compact pixels of p's row set, passes
+// p->pass + pass_plane[pixel] + k for k < n_passes; pass_plane and segments nullable.
+int tray_render_pixels_async(tray_scene_t sc, const tray_camera* cam, const tray_params* p,
+                             const uint32_t* pixels_device, int64_t n_pixels, const int32_t* pass_plane_device,
+                             int32_t n_passes, double* out_device, uint32_t* segments_device, void* stream) {
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
+    int rc = validate_params(p);
+    if (rc) return rc;
+    if (p->output != TRAY_OUT_RGB_F64)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "a pixel list renders TRAY_OUT_RGB_F64 only");
+    if (n_pixels < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative n_pixels");
+    rc = validate_passes(p, n_passes);
+    if (rc) return rc;
+    const int64_t rows = tray_params_rows(p);
+    if (rows * (int64_t)p->width > kQueryMaxRays)
+        return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one row set");
+    // n_pixels x n_passes x r <= 2^31 - 1, without overflow: each factor is below 2^63 / 2^31.
+    if (n_pixels > kQueryMaxRays || n_pixels * (int64_t)n_passes > kQueryMaxRays ||
+        n_pixels * (int64_t)n_passes > kQueryMaxRays / p->rays_per_pixel)
+        return fail(TRAY_ERR_TOO_LARGE, "n_pixels x n_passes x rays_per_pixel exceeds 2^31 - 1");
+    if (n_pixels == 0) return TRAY_OK;
+    if (!pixels_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null pixel list");
+    if (!out_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null result buffer");
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    frame_params(cam, p, (int32_t)rows, n_passes, k);
+    k.div_tile_rows = make_fastdiv((uint32_t)std::max(k.tile_rows, 1));  // row_of
+    size_t lds = 0;
+    // Stacks that do not fit beside the parked colours: the scan (query_takes_tree).
+    const QueryArgs q = query_args(k, wants_bvh(sc, p->flags), sc->bvh_bound, nullptr, 0, lds, kQueryPixels);
+    PixelArgs a{};
+    a.pixels = pixels_device;
+    a.plane = pass_plane_device;
+    a.out = out_device;
+    a.segments = segments_device;
+    a.n_pixels = (uint32_t)n_pixels;
+    a.n_groups = (uint32_t)n_pixels * (uint32_t)n_passes;  // n_pixels x n_passes x r <= 2^31 - 1, above
+    a.image_pixels = (uint32_t)k.rows * (uint32_t)k.width;
+    const uint32_t r = (uint32_t)k.spp;
+    a.g = r < (uint32_t)kQueryBlock ? r : (uint32_t)kQueryBlock;
+    a.unit = a.g <= 64u ? 64u : (uint32_t)kQueryBlock;
+    a.groups_per_unit = a.unit / a.g;
+    const uint32_t groups_per_block = a.groups_per_unit * ((uint32_t)kQueryBlock / a.unit);
+    a.rounds = (r + a.g - 1u) / a.g;
+    a.inv_spp = 1.0 / (double)k.spp;
+    const uint32_t blocks = (a.n_groups + groups_per_block - 1u) / groups_per_block;
+    TRAY_HIP(hipSetDevice(sc->device));
+    hipLaunchKernelGGL(render_pixels_kernel, dim3(blocks), dim3(kQueryBlock), lds, static_cast<hipStream_t>(stream),
+                       PixelLaunch{k, q, a});
+    TRAY_HIP(hipGetLastError());
     return TRAY_OK;
 }
 

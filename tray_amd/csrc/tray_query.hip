@@ -13,12 +13,19 @@
 // sdiv_rcp, reflect, refract, ...), and tray_query_device.hpp, over it, what one ray
 // of a query needs (query_hit, query_occluded, query_shade with its scatter_step, the
 // stack policy, query_args); the pixel-list renderer (tray_adaptive.hip) includes the
-// same two. This file holds the query kernels and their launchers (tray_query.hpp).
-// Compiled with -ffp-contract=off like every other unit.
+// same two. This file holds the query kernels and, below them, the entry points of the
+// three headers: each validates, fills KernelParams and QueryArgs (the scene through
+// tray_scene.hpp) and launches its kernel. Compiled with -ffp-contract=off like every other unit.
+
+#include <string.h>
 
 #include <algorithm>
 
+#include "../../include/tray_aov.h"
+#include "../../include/tray_debug.h"
+#include "../../include/tray_shade.h"  // includes tray_query.h
 #include "tray_query_device.hpp"
+#include "tray_scene.hpp"
 
 namespace tray {
 
@@ -242,84 +249,202 @@ __global__ __launch_bounds__(kQueryBlock) void aov_kernel(KernelParams p, QueryA
     if (a.out.index) a.out.index[i] = first;
 }
 
-hipError_t launch_camera_rays(KernelParams p, tray_ray* rays, uint32_t* ids, uint32_t n, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    p.div_tile_rows = make_fastdiv((uint32_t)std::max(p.tile_rows, 1));  // row_of
-    hipLaunchKernelGGL(camera_rays_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, p, rays, ids, n);
-    return hipGetLastError();
-}
-
-hipError_t launch_scene_hit(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays, uint32_t n,
-                            double t_end, tray_hit* hits, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    size_t lds = 0;
-    QueryArgs q = query_args(p, use_bvh, bound, rays, n, lds);
-    q.out = hits;
-    q.t_end = t_end;
-    hipLaunchKernelGGL(scene_hit_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), lds, stream, p,
-                       q);
-    return hipGetLastError();
-}
-
-hipError_t launch_ray_color(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays,
-                            const uint32_t* ids, uint32_t n, double* rgb, uint32_t* segments, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    size_t lds = 0;
-    QueryArgs q = query_args(p, use_bvh, bound, rays, n, lds);
-    q.ids = ids;
-    q.out = rgb;
-    q.segments = segments;
-    hipLaunchKernelGGL(ray_color_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), lds, stream, p,
-                       q);
-    return hipGetLastError();
-}
-
-hipError_t launch_scatter(const KernelParams& p, const tray_ray* rays, const tray_hit* hits, const uint32_t* ids,
-                          uint32_t n, uint32_t bounce, tray_scatter* out, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(scatter_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), 0, stream, p,
-                       rays, hits, ids, out, n, bounce);
-    return hipGetLastError();
-}
-
-hipError_t launch_background_hit(V3 color_a, V3 color_b, const tray_ray* rays, uint32_t n, double* rgb,
-                                 hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(background_hit_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), 0, stream,
-                       color_a, color_b, rays, rgb, n);
-    return hipGetLastError();
-}
-
-hipError_t launch_scene_occluded(const KernelParams& p, bool use_bvh, double bound, const tray_ray* rays,
-                                 const double* t_ends, uint32_t n, double t_end, uint8_t* occluded,
-                                 hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    size_t lds = 0;
-    QueryArgs q = query_args(p, use_bvh, bound, rays, n, lds);
-    q.out = occluded;
-    q.t_end = t_end;
-    hipLaunchKernelGGL(scene_occluded_kernel, dim3((n + kQueryBlock - 1u) / kQueryBlock), dim3(kQueryBlock), lds,
-                       stream, p, q, t_ends);
-    return hipGetLastError();
-}
-
-hipError_t launch_render_aov(KernelParams p, bool use_bvh, double bound, const tray_aov_buffers& out,
-                             hipStream_t stream) {
-    const uint32_t n = (uint32_t)p.rows * (uint32_t)p.width;
-    if (n == 0) return hipSuccess;
-    p.div_tile_rows = make_fastdiv((uint32_t)std::max(p.tile_rows, 1));  // row_of
-    size_t lds = 0;
-    const QueryArgs q = query_args(p, use_bvh, bound, nullptr, n, lds);
-    AovArgs a{};
-    a.out = out;
-    a.inv_spp = 1.0 / (double)p.spp;
-    a.tiles_x = ((uint32_t)p.width + 7u) / 8u;
-    a.samples = out.albedo || out.normal || out.depth || out.coverage ? (uint32_t)p.spp : 1u;
-    const uint32_t tiles = a.tiles_x * (((uint32_t)p.rows + 7u) / 8u);  // a wave each: <= 2^25 + 2^28
-    constexpr uint32_t kTilesPerBlock = kQueryBlock / 64;
-    hipLaunchKernelGGL(aov_kernel, dim3((tiles + kTilesPerBlock - 1u) / kTilesPerBlock), dim3(kQueryBlock), lds, stream,
-                       p, q, a);
-    return hipGetLastError();
-}
+// One ray per lane: the grid of n rays.
+static dim3 ray_blocks(int64_t n) { return dim3(((uint32_t)n + kQueryBlock - 1u) / kQueryBlock); }
 
 }  // namespace tray
+
+using namespace tray;
+
+// The queries read a scene and a camera through the megakernel's KernelParams (scene_params,
+// frame_params, key_params; the work queue, sample buffer and every other per-launch
+// workspace stay null: no query touches one). With wants_bvh, rays whose origin lies in
+// [-bvh_bound, bvh_bound]^3 traverse the BVH; the rest, and every ray without it, take the
+// reference-order linear scan (query_args, query_hit).
+#pragma GCC visibility push(default)
+extern "C" {
+
+// ---- ray queries (include/tray_query.h) ----------------------------------------
+int32_t tray_query_version(void) { return TRAY_QUERY_VERSION; }
+
+int tray_camera_rays_async(const tray_camera* cam, const tray_params* p, int32_t device, tray_ray* rays_device,
+                           uint32_t* ids_device, void* stream) {
+    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
+    int rc = validate_params(p);
+    if (rc) return rc;
+    const int64_t rows = tray_params_rows(p);
+    if (rows * (int64_t)p->width > kQueryMaxRays / p->rays_per_pixel)
+        return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 camera rays in one query");
+    const int64_t n = rows * (int64_t)p->width * (int64_t)p->rays_per_pixel;
+    if (n > 0 && !rays_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null ray buffer");
+    if (n == 0) return TRAY_OK;
+    rc = device_usable(device);
+    if (rc) return rc;
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    frame_params(cam, p, (int32_t)rows, 1, k);
+    k.div_tile_rows = make_fastdiv((uint32_t)std::max(k.tile_rows, 1));  // row_of
+    TRAY_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(camera_rays_kernel, dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), k, rays_device, ids_device, (uint32_t)n);
+    TRAY_HIP(hipGetLastError());
+    return TRAY_OK;
+}
+
+int tray_scene_hit_async(tray_scene_t sc, const tray_ray* rays_device, int64_t n, double t_end, int32_t flags,
+                         tray_hit* hits_device, void* stream) {
+    if (t_end != t_end) return fail(TRAY_ERR_INVALID_ARGUMENT, "t_end is NaN");
+    int rc = validate_query(sc, rays_device, n, flags, hits_device);
+    if (rc) return rc;
+    if (n == 0) return TRAY_OK;
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    size_t lds = 0;
+    QueryArgs q = query_args(k, wants_bvh(sc, flags), sc->bvh_bound, rays_device, (uint32_t)n, lds);
+    q.out = hits_device;
+    q.t_end = t_end;
+    TRAY_HIP(hipSetDevice(sc->device));
+    hipLaunchKernelGGL(scene_hit_kernel, ray_blocks(n), dim3(kQueryBlock), lds, static_cast<hipStream_t>(stream), k, q);
+    TRAY_HIP(hipGetLastError());
+    return TRAY_OK;
+}
+
+int tray_ray_color_async(tray_scene_t sc, const tray_ray* rays_device, const uint32_t* ids_device, int64_t n,
+                         int32_t max_depth, uint64_t seed, int32_t flags, double* rgb_device,
+                         uint32_t* segments_device, void* stream) {
+    if (max_depth <= 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "max_depth must be > 0");
+    int rc = validate_query(sc, rays_device, n, flags, rgb_device);
+    if (rc) return rc;
+    if (n == 0) return TRAY_OK;
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    key_params(seed, k);
+    k.max_depth = max_depth;
+    size_t lds = 0;
+    QueryArgs q = query_args(k, wants_bvh(sc, flags), sc->bvh_bound, rays_device, (uint32_t)n, lds);
+    q.ids = ids_device;
+    q.out = rgb_device;
+    q.segments = segments_device;
+    TRAY_HIP(hipSetDevice(sc->device));
+    hipLaunchKernelGGL(ray_color_kernel, ray_blocks(n), dim3(kQueryBlock), lds, static_cast<hipStream_t>(stream), k, q);
+    TRAY_HIP(hipGetLastError());
+    return TRAY_OK;
+}
+
+// ---- scatter, sky and occlusion queries (include/tray_shade.h) -------------------
+int32_t tray_shade_version(void) { return TRAY_SHADE_VERSION; }
+
+int tray_scatter_async(tray_scene_t sc, const tray_ray* rays_device, const tray_hit* hits_device,
+                       const uint32_t* ids_device, int64_t n, uint32_t bounce, uint64_t seed,
+                       tray_scatter* out_device, void* stream) {
+    int rc = validate_query(sc, rays_device, n, 0, out_device);
+    if (rc) return rc;
+    if (n > 0 && !hits_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null hit buffer");
+    if (n == 0) return TRAY_OK;
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    key_params(seed, k);
+    TRAY_HIP(hipSetDevice(sc->device));
+    hipLaunchKernelGGL(scatter_kernel, ray_blocks(n), dim3(kQueryBlock), 0, static_cast<hipStream_t>(stream), k,
+                       rays_device, hits_device, ids_device, out_device, (uint32_t)n, bounce);
+    TRAY_HIP(hipGetLastError());
+    return TRAY_OK;
+}
+
+int tray_background_hit_async(const tray_background* bg, const tray_ray* rays_device, int64_t n, double* rgb_device,
+                              int32_t device, void* stream) {
+    if (n < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative ray count");
+    if (n > kQueryMaxRays) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 rays in one query");
+    if (n > 0 && !rays_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null ray buffer");
+    if (n > 0 && !rgb_device) return fail(TRAY_ERR_INVALID_ARGUMENT, "null result buffer");
+    if (!bg) return fail(TRAY_ERR_INVALID_ARGUMENT, "null background");
+    if (n == 0) return TRAY_OK;
+    const int rc = device_usable(device);
+    if (rc) return rc;
+    TRAY_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(background_hit_kernel, ray_blocks(n), dim3(kQueryBlock), 0, static_cast<hipStream_t>(stream),
+                       V3{bg->color_a[0], bg->color_a[1], bg->color_a[2]},
+                       V3{bg->color_b[0], bg->color_b[1], bg->color_b[2]}, rays_device, rgb_device, (uint32_t)n);
+    TRAY_HIP(hipGetLastError());
+    return TRAY_OK;
+}
+
+int tray_scene_occluded_async(tray_scene_t sc, const tray_ray* rays_device, const double* t_end_device, int64_t n,
+                              double t_end, int32_t flags, uint8_t* occluded_device, void* stream) {
+    if (t_end != t_end) return fail(TRAY_ERR_INVALID_ARGUMENT, "t_end is NaN");
+    int rc = validate_query(sc, rays_device, n, flags, occluded_device);
+    if (rc) return rc;
+    if (n == 0) return TRAY_OK;
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    size_t lds = 0;
+    QueryArgs q = query_args(k, wants_bvh(sc, flags), sc->bvh_bound, rays_device, (uint32_t)n, lds);
+    q.out = occluded_device;
+    q.t_end = t_end;
+    TRAY_HIP(hipSetDevice(sc->device));
+    hipLaunchKernelGGL(scene_occluded_kernel, ray_blocks(n), dim3(kQueryBlock), lds, static_cast<hipStream_t>(stream),
+                       k, q, t_end_device);
+    TRAY_HIP(hipGetLastError());
+    return TRAY_OK;
+}
+
+// ---- first-hit feature buffers (include/tray_aov.h) -----------------------------
+int32_t tray_aov_version(void) { return TRAY_AOV_VERSION; }
+
+int tray_render_aov_async(tray_scene_t sc, const tray_camera* cam, const tray_params* p, const tray_aov_buffers* out,
+                          void* stream) {
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
+    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null feature buffers (out)");
+    int rc = validate_params(p);
+    if (rc) return rc;
+    if (!out->albedo && !out->normal && !out->depth && !out->coverage && !out->index)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "every feature buffer is null: nothing to write");
+    const int64_t rows = tray_params_rows(p);
+    if (rows * (int64_t)p->width > kQueryMaxRays)
+        return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one feature-buffer call");
+    if (rows == 0) return TRAY_OK;
+    // One lane per pixel and a loop over its samples: rows x width x rays_per_pixel has no
+    // limit here (the megakernel's 8-row band limit, band_fits, is about its item indices).
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    frame_params(cam, p, (int32_t)rows, 1, k);
+    k.div_tile_rows = make_fastdiv((uint32_t)std::max(k.tile_rows, 1));  // row_of
+    size_t lds = 0;
+    const QueryArgs q =
+        query_args(k, wants_bvh(sc, p->flags), sc->bvh_bound, nullptr, (uint32_t)k.rows * (uint32_t)k.width, lds);
+    AovArgs a{};
+    a.out = *out;  // null buffers are not written
+    a.inv_spp = 1.0 / (double)k.spp;
+    a.tiles_x = ((uint32_t)k.width + 7u) / 8u;
+    a.samples = out->albedo || out->normal || out->depth || out->coverage ? (uint32_t)k.spp : 1u;
+    const uint32_t tiles = a.tiles_x * (((uint32_t)k.rows + 7u) / 8u);  // a wave each: <= 2^25 + 2^28
+    constexpr uint32_t kTilesPerBlock = kQueryBlock / 64;
+    TRAY_HIP(hipSetDevice(sc->device));
+    hipLaunchKernelGGL(aov_kernel, dim3((tiles + kTilesPerBlock - 1u) / kTilesPerBlock), dim3(kQueryBlock), lds,
+                       static_cast<hipStream_t>(stream), k, q, a);
+    TRAY_HIP(hipGetLastError());
+    return TRAY_OK;
+}
+
+// ---- include/tray_debug.h: which launches traverse the tree ------------------------
+static_assert(TRAY_QUERY_KIND_PLAIN == kQueryPlain && TRAY_QUERY_KIND_PIXELS == kQueryPixels &&
+                  TRAY_QUERY_KIND_TEMPORAL == kQueryTemporal,
+              "tray_debug.h names the kinds of tray_query_device.hpp");
+
+int tray_debug_query_traversal(int32_t kind, int32_t stack_depth, int32_t* bvh_out) {
+    if (!bvh_out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null argument");
+    if (kind < TRAY_QUERY_KIND_PLAIN || kind > TRAY_QUERY_KIND_TEMPORAL)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "unknown query kind");
+    if (stack_depth < 0 || stack_depth > (1 << 20)) return fail(TRAY_ERR_INVALID_ARGUMENT, "stack_depth out of range");
+    *bvh_out = query_takes_tree(static_cast<QueryKind>(kind), stack_depth + kStackSlack) ? 1 : 0;
+    return TRAY_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -4,7 +4,7 @@
 // (query_hit, query_occluded) over tray_device.hpp's traversal with the queries' stack
 // policy, one recursion level of RayColor on a plain path state (query_shade with its
 // scatter_step), and the host-side launch arguments that go with them (query_args).
-// No kernel and no launcher lives here.
+// No kernel and no entry point lives here.
 //
 // The arithmetic is tray_device.hpp's, the megakernel's own. The one exception is the
 // scatter step (scatter_step and query_shade below), the twin of shade_step: that
@@ -12,8 +12,8 @@
 // arithmetic out of it would have changed the product instances ("Ray queries").
 #pragma once
 
+#include "../../include/tray_query.h"
 #include "tray_device.hpp"
-#include "tray_query.hpp"
 
 namespace tray {
 
@@ -30,7 +30,7 @@ static_assert(kQueryBlock % 64 == 0, "whole waves");
 // with these two accessors): the megakernel's layout, slot i of a lane at
 // base[i * lanes of the workgroup], for kQueryBlock lanes: stack_cap x 1 KB of LDS
 // per workgroup. No spill area: a scene whose stack does not fit takes the linear
-// scan (launch_*).
+// scan (query_args).
 struct QStack {
     static constexpr bool spill = false;
     __attribute__((address_space(3))) uint32_t* base;  // this lane's slot 0
@@ -173,7 +173,7 @@ constexpr size_t kTemporalStaticLds = 64;     // temporal_step_kernel's red[2][4
 
 // Does a launch of `kind` on a scene with a tree traverse it (true), or does every ray take
 // the linear scan because the stacks do not fit into LDS beside the kernel's own? The one
-// place that decides it: query_args for every launcher, tray_debug_query_traversal for tests.
+// place that decides it: query_args for every launch, tray_debug_query_traversal for tests.
 inline bool query_takes_tree(QueryKind kind, int32_t stack_cap) {
     const size_t beside = kind == kQueryPixels ? kPixelStaticLds : kind == kQueryTemporal ? kTemporalStaticLds : 0;
     return query_stack_bytes(stack_cap) + beside <= kQueryLdsMax;

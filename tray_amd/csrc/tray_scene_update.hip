@@ -14,15 +14,45 @@
 // each (this unit is compiled without FMA contraction, and nothing here multiplies), then
 // outward to float. A node's box is the float min / max of its children's boxes: the builder
 // takes the double union first and rounds then, and rounding is monotone, so both agree.
+//
+// The header's two entry points are at the end of the file; they reach the scene through
+// tray_scene.hpp.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
+#include <mutex>
+#include <string>
+#include <vector>
 
-#include "tray_scene_update.hpp"
+#include "../../include/tray_scene_update.h"
+#include "bvh.hpp"
+#include "tray_scene.hpp"
 
 namespace tray {
+
+// The scene's arrays as tray_scene_upload laid them out, and what the update reads.
+struct SceneUpdateArgs {
+    const double* src;  // n x {cx, cy, cz, radius}, list order
+    int32_t n;
+    double4* geo;       // list order
+    MatRec* mat;
+    int32_t has_bvh;    // 0: the fields below are unused
+    int32_t n_slots;
+    double4* bgeo;      // slot order
+    MatRec* bmat;
+    const int32_t* bidx;
+    Bvh4Node* nodes;
+    int32_t n_nodes;
+    const int32_t* leaves;
+    const uint32_t* schedule;  // refit_schedule, on the device
+    int32_t n_levels;
+    double bound;  // M of the upload
+    double pad;    // 4e-6 * M, computed on the host as the builder does
+    tray_scene_update_record* record;
+};
 
 namespace {
 
@@ -162,7 +192,13 @@ __global__ __launch_bounds__(kUpdateThreads) void scene_update_kernel(const Scen
 
 }  // namespace
 
-std::vector<uint32_t> refit_schedule(const uint32_t* refs, int32_t n_nodes, int32_t* n_levels) {
+// The order in which the inner children's boxes are recomputed, from the child references
+// `refs` (n_nodes x kBvhWidth, as in Bvh4Node::ref): n_levels + 1 level starts, then the
+// items node * kBvhWidth + slot of every slot that refers to an inner node, sorted by the
+// level of that node (0: all its children are leaves; else 1 + the highest level among its
+// inner children). Level l's items read only boxes that the leaves and the levels below l
+// wrote. Nodes are emitted pre-order (a child's index exceeds its parent's).
+static std::vector<uint32_t> refit_schedule(const uint32_t* refs, int32_t n_nodes, int32_t* n_levels) {
     const auto inner = [](uint32_t ref) { return ref != kBvhNone && !(ref & kBvhLeafBit); };
     std::vector<int32_t> level((size_t)std::max(n_nodes, 0), 0);
     std::vector<uint32_t> items;  // node * kBvhWidth + slot of the slots that refer to an inner node
@@ -186,9 +222,107 @@ std::vector<uint32_t> refit_schedule(const uint32_t* refs, int32_t n_nodes, int3
     return out;
 }
 
-hipError_t launch_scene_update(const SceneUpdateArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(scene_update_kernel, dim3(1), dim3(kUpdateThreads), 0, stream, a);
-    return hipGetLastError();
+// What both forms check before any device work; `geometry` and `record` are the device's
+// for the asynchronous form and the host's for the synchronous one.
+static int validate_update(tray_scene_t sc, const double* geometry, int32_t n_spheres,
+                           const tray_scene_update_record* record) {
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    if (!geometry) return fail(TRAY_ERR_INVALID_ARGUMENT, "null geometry");
+    if (!record) return fail(TRAY_ERR_INVALID_ARGUMENT, "null record");
+    if (n_spheres != sc->n)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "n_spheres is " + std::to_string(n_spheres) + ", the scene has " +
+                                                   std::to_string(sc->n) + ": an update keeps the sphere count");
+    return TRAY_OK;
 }
 
 }  // namespace tray
+
+using namespace tray;
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int tray_scene_update_async(tray_scene_t sc, const double* geometry_device, int32_t n_spheres,
+                            tray_scene_update_record* record_device, void* stream_arg) {
+    const int rc = validate_update(sc, geometry_device, n_spheres, record_device);
+    if (rc) return rc;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_arg);
+    TRAY_HIP(hipSetDevice(sc->device));
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if (sc->has_bvh && !sc->schedule) {  // the first update: topology only, so built once
+        int32_t n_levels = 0;
+        const std::vector<uint32_t> sched = refit_schedule(sc->refs.data(), sc->n_nodes, &n_levels);
+        uint32_t* dev = nullptr;
+        TRAY_HIP(hipMalloc(reinterpret_cast<void**>(&dev), sched.size() * sizeof(uint32_t)));
+        const hipError_t e = hipMemcpy(dev, sched.data(), sched.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(dev);
+            return hip_fail(e, "level schedule");
+        }
+        sc->schedule = dev;
+        sc->n_levels = n_levels;
+    }
+    if (!sc->updated) TRAY_HIP(hipEventCreateWithFlags(&sc->updated, hipEventDisableTiming));
+    // Renders enqueued so far read the old geometry: the update waits for each context's last
+    // one (on the device). Their candidate lists and work orders were the old geometry's.
+    for (LaunchCtx* c : sc->ctx) {
+        if (c->launched && c->last_stream != stream) TRAY_HIP(hipStreamWaitEvent(stream, c->done, 0));
+        c->cand_valid = c->order_valid = false;
+    }
+    SceneUpdateArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = geometry_device;
+    a.n = sc->n;
+    a.geo = sc->geo;
+    a.mat = sc->mat;
+    a.has_bvh = sc->has_bvh ? 1 : 0;
+    if (sc->has_bvh) {
+        a.n_slots = sc->n_slots;
+        a.bgeo = sc->bgeo;
+        a.bmat = sc->bmat;
+        a.bidx = sc->bidx;
+        a.nodes = sc->nodes;
+        a.n_nodes = sc->n_nodes;
+        a.leaves = sc->leaves;
+        a.schedule = sc->schedule;
+        a.n_levels = sc->n_levels;
+        a.bound = sc->bvh_bound;
+        a.pad = 4e-6 * sc->bvh_bound;  // Builder::pad (tray_bvh.cpp)
+    }
+    a.record = record_device;
+    // One workgroup: check, then (unless refused) geometry, leaf boxes, inner boxes level by level.
+    hipLaunchKernelGGL(scene_update_kernel, dim3(1), dim3(kUpdateThreads), 0, stream, a);
+    TRAY_HIP(hipGetLastError());
+    const hipError_t e = hipEventRecord(sc->updated, stream);
+    if (e != hipSuccess) {  // nothing marks the update's end: wait for it here
+        (void)hipStreamSynchronize(stream);
+        return hip_fail(e, "hipEventRecord");
+    }
+    sc->update_recorded = true;
+    return TRAY_OK;
+}
+
+int tray_scene_update(tray_scene_t sc, const double* geometry_host, int32_t n_spheres,
+                      tray_scene_update_record* record_out) {
+    int rc = validate_update(sc, geometry_host, n_spheres, record_out);
+    if (rc) return rc;
+    TRAY_HIP(hipSetDevice(sc->device));
+    const size_t geo_bytes = sizeof(double) * 4 * (size_t)n_spheres;
+    uint8_t* staging = nullptr;  // the record, then the geometry
+    TRAY_HIP(hipMalloc(reinterpret_cast<void**>(&staging), sizeof(tray_scene_update_record) + geo_bytes + 32));
+    tray_scene_update_record* record_device = reinterpret_cast<tray_scene_update_record*>(staging);
+    double* geometry_device = reinterpret_cast<double*>(staging + sizeof(tray_scene_update_record));
+    hipError_t e = geo_bytes ? hipMemcpy(geometry_device, geometry_host, geo_bytes, hipMemcpyHostToDevice) : hipSuccess;
+    rc = e == hipSuccess ? tray_scene_update_async(sc, geometry_device, n_spheres, record_device, nullptr)
+                         : hip_fail(e, "geometry staging");
+    if (rc == TRAY_OK) {
+        e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess) e = hipMemcpy(record_out, record_device, sizeof(*record_out), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hip_fail(e, "scene update");
+    }
+    (void)hipFree(staging);
+    return rc;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -16,13 +16,20 @@
 // traversals stay together as in aov_kernel. The taps depend on the data (the hit), so
 // the history is read through the caches, not staged; only the traversal stacks and the
 // 64 bytes of the record's reduction live in LDS.
+//
+// The entry points of both headers are at the end of the file: one function
+// (temporal_step) checks, fills and launches either instance of the step; the scene comes
+// through tray_scene.hpp, the argument checks from tray_check.hpp.
 
+#include <string.h>
+
+#include <cmath>
 #include <limits>
 
 #include "../../include/tray_temporal.h"
 #include "../../include/tray_temporal_variance.h"
-#include "tray_internal.hpp"
 #include "tray_query_device.hpp"
+#include "tray_scene.hpp"
 #include "tray_stream.hpp"
 
 namespace tray {
@@ -220,28 +227,90 @@ __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaun
 static tray_temporal_state plain_state(const tray_temporal_var_state& s) {
     return tray_temporal_state{s.colour, s.age, s.index, s.depth, s.width, s.height};
 }
+static tray_temporal_var_state without_m2(const tray_temporal_state& s) {
+    return tray_temporal_var_state{s.colour, nullptr, s.age, s.index, s.depth, s.width, s.height};
+}
 
-// The launch of either instance: out.m2 null is the plain step.
-hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, const tray_camera* prev,
-                                const tray_temporal_params& tp, const double* frame,
-                                const tray_temporal_var_state* history, const tray_temporal_var_state& out,
-                                double* variance, tray_temporal_record* record, hipStream_t stream) {
-    if (out.width <= 0 || out.height <= 0) return hipSuccess;
+// Both steps (the plain one without the M2 and variance rows): the states come as
+// tray_temporal_var_state, a plain state widened with a null m2. One reprojection step over
+// the out->width x out->height frame; `history` and `prev` both null: the first frame.
+static int temporal_step(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
+                         const tray_temporal_params* tp, const double* frame_device,
+                         const tray_temporal_var_state* history, const tray_temporal_var_state* out, bool with_m2,
+                         double* variance_device, tray_temporal_record* record_device, void* stream_arg) {
+    if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
+    if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
+    if (!tp) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params");
+    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null state (out)");
+    if ((history == nullptr) != (prev == nullptr))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "history and prev_camera must both be given or both be null");
+    if (out->width < 0 || out->height < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative width or height");
+    if (history && (history->width != out->width || history->height != out->height))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "history and out differ in width or height");
+    if (tp->max_history < 1 || tp->max_history > (1 << 30))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "max_history must be in 1 .. 2^30");
+    if (tp->flags & ~TRAY_FLAG_LINEAR_SCAN)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "unknown flags (only TRAY_FLAG_LINEAR_SCAN applies)");
+    if (!(std::isfinite(tp->depth_tolerance) && tp->depth_tolerance >= 0.0))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "depth_tolerance must be finite and >= 0");
+    if (!(std::isfinite(tp->snap) && tp->snap >= 0.0 && tp->snap < 0.5))
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "snap must be finite, >= 0 and < 0.5");
+    if (tp->reserved != 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "reserved must be 0");
+    const int64_t image = (int64_t)out->width * (int64_t)out->height;
+    if (image > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
+    if (image == 0) return TRAY_OK;
+    // The spans: outputs first (the first n_out; the variance and the record nullable), then what is only read.
+    const size_t px = (size_t)image;
+    Span spans[13];
+    int n = 0;
+    uint32_t nullable = 0;
+    spans[n++] = {out->colour, px * 24, 8, "out.colour"};
+    if (with_m2) spans[n++] = {out->m2, px * 24, 8, "out.m2"};
+    spans[n++] = {out->age, px * 4, 4, "out.age"};
+    spans[n++] = {out->index, px * 4, 4, "out.index"};
+    spans[n++] = {out->depth, px * 8, 8, "out.depth"};
+    if (with_m2) {
+        nullable |= 1u << n;
+        spans[n++] = {variance_device, px * 24, 8, "the variance"};
+    }
+    nullable |= 1u << n;
+    spans[n++] = {record_device, sizeof(tray_temporal_record), 8, "the record"};
+    const int n_out = n;
+    spans[n++] = {frame_device, px * 24, 8, "the frame"};
+    if (history) {
+        spans[n++] = {history->colour, px * 24, 8, "history.colour"};
+        if (with_m2) spans[n++] = {history->m2, px * 24, 8, "history.m2"};
+        spans[n++] = {history->age, px * 4, 4, "history.age"};
+        spans[n++] = {history->index, px * 4, 4, "history.index"};
+        spans[n++] = {history->depth, px * 8, 8, "history.depth"};
+    }
+    int rc = check_nulls(spans, n, nullable);
+    if (!rc) rc = check_alignment(spans, n);
+    if (!rc) rc = check_overlaps(spans, n, n_out);
+    if (rc) return rc;
+    KernelParams k;
+    memset(&k, 0, sizeof(k));
+    scene_params(sc, k);
+    camera_params(cam, k);
+    k.width = out->width;
+    k.height = out->height;
+    k.rows = out->height;
     size_t lds = 0;
     // Stacks that do not fit beside the reduction: the scan (query_takes_tree).
-    const QueryArgs q = query_args(p, use_bvh, bound, nullptr, 0, lds, kQueryTemporal);
+    const QueryArgs q = query_args(k, wants_bvh(sc, tp->flags), sc->bvh_bound, nullptr, 0, lds, kQueryTemporal);
     TemporalArgs a{};
-    a.frame = frame;
-    a.out = plain_state(out);
-    a.record = record;
-    a.depth_tolerance = tp.depth_tolerance;
-    a.snap = tp.snap;
-    a.max_history = tp.max_history;
-    a.out_m2 = out.m2;
-    a.variance = variance;
-    if (history && prev && tp.max_history > 1) {  // max_history 1: the frame itself (the header, section 3)
+    a.frame = frame_device;
+    a.out = plain_state(*out);
+    a.record = record_device;
+    a.depth_tolerance = tp->depth_tolerance;
+    a.snap = tp->snap;
+    a.max_history = tp->max_history;
+    a.out_m2 = out->m2;  // null in the plain step, as history's m2 and the variance
+    a.variance = variance_device;
+    if (history && tp->max_history > 1) {  // max_history 1: the frame itself (the header, section 3)
         a.history = plain_state(*history);
         a.history_m2 = history->m2;
+        // The previous camera: what does not depend on the pixel, in the header's operations and order.
         PrevCamera& P = a.prev;
         for (int c = 0; c < 3; ++c) {
             P.position[c] = prev->position[c];
@@ -254,18 +323,19 @@ hipError_t launch_temporal_step(KernelParams p, bool use_bvh, double bound, cons
         P.xx = dot3(P.pixel_x, P.pixel_x);
         P.yy = dot3(P.pixel_y, P.pixel_y);
     }
-    a.tiles_x = ((uint32_t)out.width + kTileX - 1u) / kTileX;
-    const uint32_t tiles_y = ((uint32_t)out.height + kTileY - 1u) / kTileY;  // tiles_x x tiles_y <= 2^26 + 2^28
-    hipError_t e = hipSuccess;
-    if (record) e = hipMemsetAsync(record, 0, sizeof(*record), stream);
-    if (e != hipSuccess) return e;
-    if (out.m2)
+    a.tiles_x = ((uint32_t)out->width + kTileX - 1u) / kTileX;
+    const uint32_t tiles_y = ((uint32_t)out->height + kTileY - 1u) / kTileY;  // tiles_x x tiles_y <= 2^26 + 2^28
+    const hipStream_t stream = static_cast<hipStream_t>(stream_arg);
+    TRAY_HIP(hipSetDevice(sc->device));
+    if (record_device) TRAY_HIP(hipMemsetAsync(record_device, 0, sizeof(*record_device), stream));
+    if (with_m2)
         hipLaunchKernelGGL(temporal_step_kernel<true>, dim3(a.tiles_x * tiles_y), dim3(kQueryBlock), lds, stream,
-                           TemporalLaunch{p, q, a});
+                           TemporalLaunch{k, q, a});
     else
         hipLaunchKernelGGL(temporal_step_kernel<false>, dim3(a.tiles_x * tiles_y), dim3(kQueryBlock), lds, stream,
-                           TemporalLaunch{p, q, a});
-    return hipGetLastError();
+                           TemporalLaunch{k, q, a});
+    TRAY_HIP(hipGetLastError());
+    return TRAY_OK;
 }
 
 // ---- include/tray_temporal_variance.h section 3: the variance of the mean from (m2, age) ----
@@ -317,28 +387,90 @@ __global__ __launch_bounds__(kThreads) void temporal_variance_list_kernel(const 
     v[0] = variance_of_mean(m0, n), v[1] = variance_of_mean(m1, n), v[2] = variance_of_mean(m2, n);
 }
 
-hipError_t launch_temporal_variance(const double* m2, const int32_t* age, uint32_t image_pixels,
-                                    const uint32_t* pixels, uint32_t n_pixels, double* variance,
-                                    hipStream_t stream) {
-    VarianceArgs a{};
-    a.m2 = m2;
-    a.age = age;
-    a.pixels = pixels;
-    a.variance = variance;
-    a.image_pixels = image_pixels;
-    if (pixels) {
-        if (n_pixels == 0 || image_pixels == 0) return hipSuccess;
-        a.n_pixels = n_pixels;
-        const uint32_t blocks = (n_pixels + (uint32_t)kThreads - 1u) / (uint32_t)kThreads;  // <= 2^23
-        hipLaunchKernelGGL(temporal_variance_list_kernel, dim3(blocks), dim3(kThreads), 0, stream, a);
-    } else {
-        if (image_pixels == 0) return hipSuccess;
-        a.elems = (size_t)image_pixels * 3;
-        a.chunks = (a.elems + kBlockElems - 1) / kBlockElems;
-        const int64_t grid = (int64_t)a.chunks < kMaxGrid ? (int64_t)a.chunks : kMaxGrid;
-        hipLaunchKernelGGL(temporal_variance_frame_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, stream, a);
-    }
-    return hipGetLastError();
+}  // namespace tray
+
+using namespace tray;
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+// ---- temporal reprojection (include/tray_temporal.h) -----------------------------
+int32_t tray_temporal_version(void) { return TRAY_TEMPORAL_VERSION; }
+
+int tray_temporal_default_params(tray_temporal_params* out) {
+    if (!out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params (out)");
+    out->max_history = 32;       // tools/temporal_sweep.py, DESIGN.md 8q
+    out->flags = 0;
+    out->depth_tolerance = 0.1;  // the same sweep
+    out->snap = 0x1.0p-20;
+    out->reserved = 0;
+    return TRAY_OK;
 }
 
-}  // namespace tray
+int tray_temporal_step_async(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
+                             const tray_temporal_params* tp, const double* frame_device,
+                             const tray_temporal_state* history, const tray_temporal_state* out,
+                             tray_temporal_record* record_device, void* stream) {
+    tray_temporal_var_state h{}, o{};
+    if (history) h = without_m2(*history);
+    if (out) o = without_m2(*out);
+    return temporal_step(sc, cam, prev, tp, frame_device, history ? &h : nullptr, out ? &o : nullptr, false, nullptr,
+                         record_device, stream);
+}
+
+// ---- temporal reprojection with M2 (include/tray_temporal_variance.h) --------------
+int32_t tray_temporal_var_version(void) { return TRAY_TEMPORAL_VAR_VERSION; }
+
+int tray_temporal_var_step_async(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
+                                 const tray_temporal_params* tp, const double* frame_device,
+                                 const tray_temporal_var_state* history, const tray_temporal_var_state* out,
+                                 double* variance_device, tray_temporal_record* record_device, void* stream) {
+    return temporal_step(sc, cam, prev, tp, frame_device, history, out, true, variance_device, record_device, stream);
+}
+
+// Section 3: the variance of the mean of the n_pixels listed pixels (entries beyond the image
+// skipped), or of every pixel when `pixels_device` is null.
+int tray_temporal_var_variance_async(const tray_temporal_var_state* state, const uint32_t* pixels_device,
+                                     int64_t n_pixels, double* variance_device, int32_t device, void* stream) {
+    if (!state) return fail(TRAY_ERR_INVALID_ARGUMENT, "null state");
+    if (state->width < 0 || state->height < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative width or height");
+    if (pixels_device && n_pixels < 0) return fail(TRAY_ERR_INVALID_ARGUMENT, "negative n_pixels");
+    const int64_t image = (int64_t)state->width * (int64_t)state->height;
+    if (image > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "more than 2^31 - 1 pixels in one state");
+    if (pixels_device && n_pixels > kMaxPixels) return fail(TRAY_ERR_TOO_LARGE, "n_pixels exceeds 2^31 - 1");
+    if (image == 0 || (pixels_device && n_pixels == 0)) return TRAY_OK;
+    const size_t px = (size_t)image;
+    const Span spans[4] = {{variance_device, px * 24, 8, "the variance"},
+                           {state->m2, px * 24, 8, "m2"},
+                           {state->age, px * 4, 4, "age"},
+                           {pixels_device, pixels_device ? (size_t)n_pixels * 4 : 0, 4, "the pixel list"}};
+    int rc = check_nulls(spans, 4, 1u << 3);
+    if (!rc) rc = check_alignment(spans, 4);
+    if (!rc) rc = check_overlaps(spans, 4, 1);
+    if (!rc) rc = device_usable(device);
+    if (rc) return rc;
+    VarianceArgs a{};
+    a.m2 = state->m2;
+    a.age = state->age;
+    a.pixels = pixels_device;
+    a.variance = variance_device;
+    a.image_pixels = (uint32_t)image;
+    TRAY_HIP(hipSetDevice(device));
+    if (pixels_device) {
+        a.n_pixels = (uint32_t)n_pixels;
+        const uint32_t blocks = (a.n_pixels + (uint32_t)kThreads - 1u) / (uint32_t)kThreads;  // <= 2^23
+        hipLaunchKernelGGL(temporal_variance_list_kernel, dim3(blocks), dim3(kThreads), 0,
+                           static_cast<hipStream_t>(stream), a);
+    } else {
+        a.elems = (size_t)a.image_pixels * 3;
+        a.chunks = (a.elems + kBlockElems - 1) / kBlockElems;
+        const int64_t grid = (int64_t)a.chunks < kMaxGrid ? (int64_t)a.chunks : kMaxGrid;
+        hipLaunchKernelGGL(temporal_variance_frame_kernel, dim3((uint32_t)grid), dim3(kThreads), 0,
+                           static_cast<hipStream_t>(stream), a);
+    }
+    TRAY_HIP(hipGetLastError());
+    return TRAY_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop
