@@ -61,9 +61,11 @@
  * 5. STATE DERIVED FROM THE OLD GEOMETRY. The library's own (the primary-ray
  *    candidate lists and the work order of the scene's launch contexts) is
  *    invalidated by the call, also by a refused one. The caller's is stale and the
- *    caller's to reset: a tray_temporal_state holds index and depth planes of the
- *    old geometry (reprojection across an update is not supported), and adaptive
- *    and progressive accumulators hold means of the old scene's frames.
+ *    caller's: a tray_temporal_state holds index and depth planes of the old
+ *    geometry, which tray_temporal_motion.h carries across the update given the
+ *    geometry the scene held before it (tray_temporal_step_async itself assumes a
+ *    static scene); adaptive and progressive accumulators hold means of the old
+ *    scene's frames and are the caller's to reset.
  */
 #ifndef TRAY_SCENE_UPDATE_H
 #define TRAY_SCENE_UPDATE_H

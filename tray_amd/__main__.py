@@ -18,6 +18,9 @@ have no meaning here).
     python -m tray_amd -r 16 -bounce 8 [-denoise] ...  # the small spheres hop: one upload, then per frame the
                                           # spheres moved and the BVH refitted on the device
                                           # (include/tray_scene_update.h)
+    python -m tray_amd -r 4 -bounce 8 -temporal [-variance] [-refill [R]] [-denoise] ...  # the same, each frame
+                                          # reusing the last: the history follows the hopping spheres
+                                          # (include/tray_temporal_motion.h)
 """
 from __future__ import annotations
 
@@ -76,16 +79,21 @@ def main(argv=None) -> int:
     ap.add_argument("-orbit-step", type=float, default=ray.ORBIT_STEP_DEGREES, metavar="DEG", dest="orbit_step",
                     help="with -orbit: degrees between frames")
     ap.add_argument("-variance", action="store_true",
-                    help="with -orbit: carry M2 with the colour (include/tray_temporal_variance.h); -denoise is then "
-                         "the variance-guided filter")
+                    help="with -orbit or -bounce -temporal: carry M2 with the colour "
+                         "(include/tray_temporal_variance.h); -denoise is then the variance-guided filter")
     ap.add_argument("-refill", type=int, nargs="?", default=0, const=ray.REFILL_DEFAULT, metavar="R",
-                    help="with -orbit -variance: R more passes per frame for the pixels that hold fewer than 1 + R "
+                    help="with -orbit -variance or -bounce -temporal -variance: R more passes per frame for the pixels "
+                         "that hold fewer than 1 + R "
                          f"frames and their neighbours (default R when given without a number: {ray.REFILL_DEFAULT}); "
                          "prints the refilled pixels per frame")
     ap.add_argument("-bounce", type=int, default=0, metavar="N",
                     help="render N frames in which the small spheres hop (y = R + |sin| of a phase per sphere), "
                          "moved in place on the device with the BVH refitted (include/tray_scene_update.h); prints "
                          "per frame whether the update was applied and saves the last frame; -denoise applies")
+    ap.add_argument("-temporal", action="store_true",
+                    help="with -bounce: each frame reuses the last through temporal reprojection that follows the "
+                         "moved spheres (include/tray_temporal_motion.h); prints the fresh fraction and the mean age "
+                         "per frame; -variance, -refill and -denoise apply as with -orbit")
     ap.add_argument("-ansi", action="store_true",
                     help="render at -s x the terminal size and draw it in the terminal (main.go:86-131)")
     ap.add_argument("-s", type=float, default=4, help="supersampling factor of -ansi")
@@ -100,13 +108,23 @@ def main(argv=None) -> int:
     samples = a.width * a.height * a.r
     if a.orbit < 0 or (a.orbit and (a.passes or a.adaptive)):
         ap.error("-orbit needs N >= 1 and goes with neither -passes nor -adaptive")
-    if (a.variance or a.refill) and not a.orbit:
-        ap.error("-variance and -refill go with -orbit N")
+    if a.temporal and not a.bounce:
+        ap.error("-temporal goes with -bounce N")
+    if (a.variance or a.refill) and not (a.orbit or a.temporal):
+        ap.error("-variance and -refill go with -orbit N or -bounce N -temporal")
     if a.refill < 0 or (a.refill and not a.variance):
         ap.error("-refill needs R >= 0 and -variance")
     if a.bounce < 0 or (a.bounce and (a.orbit or a.passes or a.adaptive)):
         ap.error("-bounce needs N >= 1 and goes with none of -orbit, -passes and -adaptive")
-    if a.bounce:
+    if a.bounce and a.temporal:
+        img = t.RenderAnimation(scene, ray.Bounce(scene, a.bounce), denoise=a.denoise, temporal=True,
+                                variance=a.variance, refill=a.refill)[-1]
+        refilled = t.refilled if a.variance else [None] * a.bounce
+        for k, (fresh, age, n) in enumerate(zip(t.fresh, t.mean_age, refilled)):
+            print(f"frame {k}: fresh {fresh / max(a.width * a.height, 1):.4f} mean age {age:.3f}" +
+                  (f" refilled {n}" if a.variance else ""))
+        samples *= t.pixel_passes / max(a.width * a.height, 1) if a.variance else a.bounce
+    elif a.bounce:
         img = t.RenderAnimation(scene, ray.Bounce(scene, a.bounce), denoise=a.denoise)[-1]
         for k, applied in enumerate(t.applied):
             print(f"frame {k}: {'moved in place' if applied else 'refused: uploaded afresh'}")

@@ -382,6 +382,13 @@ class TemporalVarState(ctypes.Structure):
 
 assert ctypes.sizeof(TemporalVarState) == 48
 
+# Every symbol include/tray_temporal_motion.h declares (the reprojection step across a scene update:
+# history follows the moved spheres; in none of the lists above).
+TEMPORAL_MOTION_EXPORTS = (
+    "tray_temporal_motion_version",
+    "tray_temporal_motion_step_async",
+)
+
 # include/tray_scene_update.h: new centres and radii for an uploaded scene, its BVH refitted on the
 # device (in none of the lists above).
 SCENE_UPDATE_EXPORTS = ("tray_scene_update_async", "tray_scene_update")
@@ -542,6 +549,12 @@ def lib(path: str | None = None) -> ctypes.CDLL:
                                                    ctypes.POINTER(TemporalVarState), vp, vp, vp]
         L.tray_temporal_var_variance_async.argtypes = [ctypes.POINTER(TemporalVarState), vp, ctypes.c_int64, vp, i32,
                                                        vp]
+    if hasattr(L, "tray_temporal_motion_version"):  # include/tray_temporal_motion.h; absent from older builds
+        L.tray_temporal_motion_version.restype = i32
+        L.tray_temporal_motion_step_async.argtypes = [vp, ctypes.POINTER(CameraState), ctypes.POINTER(CameraState),
+                                                      vp, i32, ctypes.POINTER(TemporalParams), vp,
+                                                      ctypes.POINTER(TemporalVarState),
+                                                      ctypes.POINTER(TemporalVarState), vp, vp, vp, vp]
     if hasattr(L, "tray_scene_update_async"):  # include/tray_scene_update.h; absent from older builds (A/B tools)
         L.tray_scene_update_async.argtypes = [vp, vp, i32, vp, vp]
         L.tray_scene_update.argtypes = [vp, vp, i32, ctypes.POINTER(SceneUpdateRecord)]
@@ -974,6 +987,26 @@ def temporal_var_step_async(scene_handle: int | None, camera: CameraState | None
                                              ctypes.byref(params), frame_ptr,
                                              ctypes.byref(history) if history is not None else None,
                                              ctypes.byref(out), variance_ptr, record_ptr, stream))
+
+
+def temporal_motion_step_async(scene_handle: int | None, camera: CameraState | None, prev_camera: CameraState | None,
+                               prev_geometry_ptr: int | None, n_spheres: int, params: TemporalParams,
+                               frame_ptr: int | None, history: TemporalVarState | None, out: TemporalVarState,
+                               variance_ptr: int | None = None, motion_ptr: int | None = None,
+                               record_ptr: int | None = None, stream: int | None = None,
+                               lib_path: str | None = None) -> None:
+    """tray_temporal_motion_step_async: the temporal step on a scene whose spheres moved since `history`
+    was made. The scene holds the current geometry; prev_geometry_ptr -> n_spheres x {cx, cy, cz, radius}
+    f64 on the device, what it held then. States with m2 (all or none of them) take the step of
+    temporal_var_step_async, states without (m2 None) that of temporal_step_async; motion_ptr
+    (height x width x 2 f64, nullable) receives the screen-space motion vectors. Only enqueues on
+    `stream`."""
+    L = lib(lib_path)
+    _raise(L, L.tray_temporal_motion_step_async(scene_handle, ctypes.byref(camera) if camera is not None else None,
+                                                ctypes.byref(prev_camera) if prev_camera is not None else None,
+                                                prev_geometry_ptr, int(n_spheres), ctypes.byref(params), frame_ptr,
+                                                ctypes.byref(history) if history is not None else None,
+                                                ctypes.byref(out), variance_ptr, motion_ptr, record_ptr, stream))
 
 
 def temporal_var_variance_async(state: TemporalVarState, pixels_ptr: int | None, n_pixels: int,

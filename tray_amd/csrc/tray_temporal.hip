@@ -4,7 +4,9 @@
 // frame into it and counts the record's two sums. A second instance of the same kernel
 // (include/tray_temporal_variance.h) carries M2 with the colour and writes the variance
 // of the mean in the same launch; a small streaming kernel writes that variance again
-// for a list of pixels, or for the whole frame, after a fold from outside the step.
+// for a list of pixels, or for the whole frame, after a fold from outside the step. A
+// third and a fourth instance (include/tray_temporal_motion.h) follow a hit point with its
+// sphere when the spheres have moved since the history was made, with or without M2.
 //
 // The traversal is tray_query_device.hpp's over tray_device.hpp, the megakernel's own
 // arithmetic; the projection and the fold are plain FP64 in the header's order. Compiled
@@ -17,8 +19,8 @@
 // the history is read through the caches, not staged; only the traversal stacks and the
 // 64 bytes of the record's reduction live in LDS.
 //
-// The entry points of both headers are at the end of the file: one function
-// (temporal_step) checks, fills and launches either instance of the step; the scene comes
+// The entry points of the three headers are at the end of the file: one function
+// (temporal_step) checks, fills and launches any instance of the step; the scene comes
 // through tray_scene.hpp, the argument checks from tray_check.hpp.
 
 #include <string.h>
@@ -27,6 +29,7 @@
 #include <limits>
 
 #include "../../include/tray_temporal.h"
+#include "../../include/tray_temporal_motion.h"
 #include "../../include/tray_temporal_variance.h"
 #include "tray_query_device.hpp"
 #include "tray_scene.hpp"
@@ -60,6 +63,9 @@ struct TemporalArgs {
     const double* history_m2;
     double* out_m2;
     double* variance;  // nullable
+    // The motion instances alone (after those, for the same reason):
+    const double* prev_geometry;  // n x {cx, cy, cz, radius}, list order; null only where no ray can hit
+    double* motion;               // nullable, height x width x 2
 };
 
 // The kernel's one argument: KernelParams first, where kp_fresh() reads it.
@@ -91,7 +97,11 @@ __host__ __device__ inline double dot3(const double u[3], const double v[3]) {
 // kM2: the step of include/tray_temporal_variance.h. What it adds reads nothing the plain step
 // decides on and feeds nothing back into it, so colour, age, index, depth and the record are
 // the plain instance's.
-template <bool kM2>
+//
+// kMotion: the step of include/tray_temporal_motion.h. Section 2b alone differs: the target of
+// a hit on a sphere that has moved since the history was made is the same surface point on the
+// previous sphere. With both flags false the code is the plain step's, instruction for instruction.
+template <bool kM2, bool kMotion>
 __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaunch L) {
     __shared__ unsigned long long red[2][kQueryBlock / 64];
     static_assert(sizeof(red) <= kTemporalStaticLds, "query_takes_tree counts this kernel's static LDS");
@@ -129,12 +139,38 @@ __global__ __launch_bounds__(kQueryBlock) void temporal_step_kernel(TemporalLaun
         if (a.history.colour) {
             // b. the target, c. its projection into the previous camera
             const PrevCamera& P = a.prev;
-            const D3 e = idx >= 0 ? sub(add(o, smul(d, t)), ld3(P.position)) : d;
+            D3 e = d;
+            if (idx >= 0) {
+                D3 Q = add(o, smul(d, t));
+                if constexpr (kMotion) {
+                    // The hit sphere as the scene holds it now (by slot on the tree path, by list
+                    // index on the scan path) and as it was, by list index: data dependent, so
+                    // through the caches like the taps.
+                    const KernelParams& pk = kp_fresh();
+                    const double4 g = h.tree ? pk.bgeo[h.ref] : pk.geo[h.ref];
+                    const double R = h.tree ? pk.bmat[h.ref].radius : pk.mat[h.ref].radius;
+                    const double* pg = a.prev_geometry + (size_t)idx * 4;
+                    const double pcx = pg[0], pcy = pg[1], pcz = pg[2], pR = pg[3];
+                    if (!(pcx == g.x && pcy == g.y && pcz == g.z && pR == R)) {
+                        const D3 m = sdiv(sub(Q, d3(g.x, g.y, g.z)), R);  // ray/objects.go:100
+                        Q = add(d3(pcx, pcy, pcz), smul(m, pR));
+                    }
+                }
+                e = sub(Q, ld3(P.position));
+            }
             const D3 c0 = ld3(P.c0), pxv = ld3(P.pixel_x), pyv = ld3(P.pixel_y);
             const double z = dot(ld3(P.n), e) / P.n_c0;
             const D3 g = sub(sdiv(e, z), c0);
             const double u = dot(g, pxv) / P.xx, v = dot(g, pyv) / P.yy;
-            if (z > 0.0 && u > -1.0 && u < (double)width && v > -1.0 && v < (double)height) {
+            const bool in_range = z > 0.0 && u > -1.0 && u < (double)width && v > -1.0 && v < (double)height;
+            if constexpr (kMotion) {
+                if (a.motion) {
+                    double* mv = a.motion + pix * 2;
+                    mv[0] = in_range ? u - (double)x : __builtin_nan("");
+                    mv[1] = in_range ? v - (double)y : __builtin_nan("");
+                }
+            }
+            if (in_range) {
                 // d. the taps: the snapped case is the bilinear one with weights 1, 0, 0, 0 at (xr, yr)
                 const double xr = __builtin_floor(u + 0.5), yr = __builtin_floor(v + 0.5);
                 const bool snapped = __builtin_fabs(u - xr) <= a.snap && __builtin_fabs(v - yr) <= a.snap;
@@ -231,13 +267,22 @@ static tray_temporal_var_state without_m2(const tray_temporal_state& s) {
     return tray_temporal_var_state{s.colour, nullptr, s.age, s.index, s.depth, s.width, s.height};
 }
 
-// Both steps (the plain one without the M2 and variance rows): the states come as
+// What tray_temporal_motion_step_async alone takes.
+struct MotionArgs {
+    const double* prev_geometry;
+    int32_t n_spheres;
+    double* plane;  // the motion plane, nullable
+};
+
+// All steps (the plain ones without the M2 and variance rows): the states come as
 // tray_temporal_var_state, a plain state widened with a null m2. One reprojection step over
 // the out->width x out->height frame; `history` and `prev` both null: the first frame.
+// `mo` non-null: the step of include/tray_temporal_motion.h.
 static int temporal_step(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
                          const tray_temporal_params* tp, const double* frame_device,
                          const tray_temporal_var_state* history, const tray_temporal_var_state* out, bool with_m2,
-                         double* variance_device, tray_temporal_record* record_device, void* stream_arg) {
+                         double* variance_device, tray_temporal_record* record_device, void* stream_arg,
+                         const MotionArgs* mo = nullptr) {
     if (!sc) return fail(TRAY_ERR_INVALID_ARGUMENT, "null scene");
     if (!cam) return fail(TRAY_ERR_INVALID_ARGUMENT, "null camera");
     if (!tp) return fail(TRAY_ERR_INVALID_ARGUMENT, "null params");
@@ -261,7 +306,7 @@ static int temporal_step(tray_scene_t sc, const tray_camera* cam, const tray_cam
     if (image == 0) return TRAY_OK;
     // The spans: outputs first (the first n_out; the variance and the record nullable), then what is only read.
     const size_t px = (size_t)image;
-    Span spans[13];
+    Span spans[15];
     int n = 0;
     uint32_t nullable = 0;
     spans[n++] = {out->colour, px * 24, 8, "out.colour"};
@@ -275,8 +320,14 @@ static int temporal_step(tray_scene_t sc, const tray_camera* cam, const tray_cam
     }
     nullable |= 1u << n;
     spans[n++] = {record_device, sizeof(tray_temporal_record), 8, "the record"};
+    if (mo) {
+        nullable |= 1u << n;
+        spans[n++] = {mo->plane, px * 16, 8, "the motion plane"};
+    }
     const int n_out = n;
     spans[n++] = {frame_device, px * 24, 8, "the frame"};
+    if (mo && history && mo->n_spheres > 0)  // ignored on the first frame; never read without a sphere to hit
+        spans[n++] = {mo->prev_geometry, (size_t)mo->n_spheres * 32, 8, "the previous geometry"};
     if (history) {
         spans[n++] = {history->colour, px * 24, 8, "history.colour"};
         if (with_m2) spans[n++] = {history->m2, px * 24, 8, "history.m2"};
@@ -288,6 +339,8 @@ static int temporal_step(tray_scene_t sc, const tray_camera* cam, const tray_cam
     if (!rc) rc = check_alignment(spans, n);
     if (!rc) rc = check_overlaps(spans, n, n_out);
     if (rc) return rc;
+    if (mo && mo->n_spheres != sc->n)  // the first look at the scene
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "n_spheres differs from the scene's sphere count");
     KernelParams k;
     memset(&k, 0, sizeof(k));
     scene_params(sc, k);
@@ -310,6 +363,7 @@ static int temporal_step(tray_scene_t sc, const tray_camera* cam, const tray_cam
     if (history && tp->max_history > 1) {  // max_history 1: the frame itself (the header, section 3)
         a.history = plain_state(*history);
         a.history_m2 = history->m2;
+        if (mo) a.prev_geometry = mo->prev_geometry, a.motion = mo->plane;
         // The previous camera: what does not depend on the pixel, in the header's operations and order.
         PrevCamera& P = a.prev;
         for (int c = 0; c < 3; ++c) {
@@ -328,12 +382,12 @@ static int temporal_step(tray_scene_t sc, const tray_camera* cam, const tray_cam
     const hipStream_t stream = static_cast<hipStream_t>(stream_arg);
     TRAY_HIP(hipSetDevice(sc->device));
     if (record_device) TRAY_HIP(hipMemsetAsync(record_device, 0, sizeof(*record_device), stream));
-    if (with_m2)
-        hipLaunchKernelGGL(temporal_step_kernel<true>, dim3(a.tiles_x * tiles_y), dim3(kQueryBlock), lds, stream,
-                           TemporalLaunch{k, q, a});
-    else
-        hipLaunchKernelGGL(temporal_step_kernel<false>, dim3(a.tiles_x * tiles_y), dim3(kQueryBlock), lds, stream,
-                           TemporalLaunch{k, q, a});
+    const dim3 grid(a.tiles_x * tiles_y), block(kQueryBlock);
+    const TemporalLaunch launch{k, q, a};
+    if (mo && with_m2) hipLaunchKernelGGL((temporal_step_kernel<true, true>), grid, block, lds, stream, launch);
+    else if (mo) hipLaunchKernelGGL((temporal_step_kernel<false, true>), grid, block, lds, stream, launch);
+    else if (with_m2) hipLaunchKernelGGL((temporal_step_kernel<true, false>), grid, block, lds, stream, launch);
+    else hipLaunchKernelGGL((temporal_step_kernel<false, false>), grid, block, lds, stream, launch);
     TRAY_HIP(hipGetLastError());
     return TRAY_OK;
 }
@@ -426,6 +480,25 @@ int tray_temporal_var_step_async(tray_scene_t sc, const tray_camera* cam, const 
                                  const tray_temporal_var_state* history, const tray_temporal_var_state* out,
                                  double* variance_device, tray_temporal_record* record_device, void* stream) {
     return temporal_step(sc, cam, prev, tp, frame_device, history, out, true, variance_device, record_device, stream);
+}
+
+// ---- temporal reprojection across scene updates (include/tray_temporal_motion.h) ----
+int32_t tray_temporal_motion_version(void) { return TRAY_TEMPORAL_MOTION_VERSION; }
+
+int tray_temporal_motion_step_async(tray_scene_t sc, const tray_camera* cam, const tray_camera* prev,
+                                    const double* prev_geometry_device, int32_t n_spheres,
+                                    const tray_temporal_params* tp, const double* frame_device,
+                                    const tray_temporal_var_state* history, const tray_temporal_var_state* out,
+                                    double* variance_device, double* motion_device,
+                                    tray_temporal_record* record_device, void* stream) {
+    const bool with_m2 = out && out->m2;
+    if (out && history && (history->m2 != nullptr) != with_m2)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "the m2 planes of history and out must all be given or all be null");
+    if (out && variance_device && !with_m2)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "a variance plane needs the m2 planes");
+    const MotionArgs mo{prev_geometry_device, n_spheres, motion_device};
+    return temporal_step(sc, cam, prev, tp, frame_device, history, out, with_m2, variance_device, record_device,
+                         stream, &mo);
 }
 
 // Section 3: the variance of the mean of the n_pixels listed pixels (entries beyond the image

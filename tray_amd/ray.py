@@ -439,6 +439,152 @@ def _given(**kw) -> dict:
     return {name: value for name, value in kw.items() if value is not None}
 
 
+def _refill_options(refill, refill_tolerance, refill_dilate) -> tuple:
+    """(refill as an int, refill_tolerance as a float) of RenderSequence's and RenderAnimation's
+    arguments; ValueError for what they refuse."""
+    if isinstance(refill, bool) or not isinstance(refill, (int, np.integer)) or refill < 0:
+        raise ValueError("refill must be an integer >= 0")
+    if refill_dilate not in (0, 1):
+        raise ValueError("refill_dilate must be 0 or 1")
+    rt = float(refill_tolerance)
+    if not (rt >= 0.0 and rt * rt < float("inf")):
+        raise ValueError("refill_tolerance must be finite and >= 0, with a finite square")
+    return int(refill), rt
+
+
+def _temporal_options(overrides: dict, refill: int) -> "_lib.TemporalParams":
+    """tray_temporal_params with the same methods' overrides; ValueError for an unknown one and for a
+    refill that max_history leaves no room for."""
+    unknown = sorted(set(overrides) - {n for n, _ in _lib.TemporalParams._fields_})
+    if unknown or "reserved" in overrides:
+        raise ValueError(f"unknown temporal parameters {unknown or ['reserved']}")
+    tp = _lib.temporal_params(**overrides)
+    if refill and tp.max_history < 1 + refill:
+        raise ValueError(f"refill={refill} needs max_history >= {1 + refill}: no pixel could hold "
+                         f"1 + refill frames (max_history is {tp.max_history})")
+    return tp
+
+
+class _TemporalLoop:
+    """The frame body Tracer.RenderSequence and Tracer.RenderAnimation(temporal=True) share: the
+    buffers of `count` frames (two ping-pong states, the frame, the records, the RGBA frames, with
+    `variance` the variance plane, with `refill` the selection's workspace and the list renderer's
+    values, with `denoise` the guides), one frame enqueued on `stream` per call of frame(), and the
+    readback into the tracer's fields in finish()."""
+
+    def __init__(self, tracer, torch, device, where, stream, count, tp, variance, refill, refill_tolerance,
+                 refill_dilate, denoise):
+        self.t, self.torch, self.device, self.where, self.stream = tracer, torch, device, where, stream
+        self.count, self.tp, self.variance, self.refill, self.denoise = count, tp, variance, refill, denoise
+        h, w = tracer.height, tracer.width
+        f64 = dict(dtype=torch.float64, device=where)
+
+        def planes():
+            t = dict(colour=torch.empty((h, w, 3), **f64), age=torch.empty((h, w), dtype=torch.int32, device=where),
+                     index=torch.empty((h, w), dtype=torch.int32, device=where), depth=torch.empty((h, w), **f64))
+            if variance:
+                t["m2"] = torch.empty((h, w, 3), **f64)
+                return t, _lib.TemporalVarState(t["colour"].data_ptr(), t["m2"].data_ptr(), t["age"].data_ptr(),
+                                                t["index"].data_ptr(), t["depth"].data_ptr(), w, h)
+            return t, _lib.TemporalState(t["colour"].data_ptr(), t["age"].data_ptr(), t["index"].data_ptr(),
+                                         t["depth"].data_ptr(), w, h)
+
+        self.states = [planes(), planes()]
+        self.frame_buffer = torch.empty((h, w, 3), **f64)
+        self.records = torch.empty((count, 2), dtype=torch.int64, device=where)
+        self.rgba = torch.empty((count, h, w, 4), dtype=torch.uint8, device=where)
+        self.aov = tracer._guide_buffers(torch, where) if denoise else None
+        self.var_plane = torch.empty((h, w, 3), **f64) if variance else None
+        if refill:
+            self.ap = _lib.adaptive_params(tolerance=refill_tolerance, min_passes=1 + refill,
+                                           max_passes=int(tp.max_history), dilate=int(refill_dilate))
+            self.nbytes = _lib.adaptive_workspace_bytes(w, h)
+            self.work = torch.empty((self.nbytes // 8,), **f64)
+            self.active = torch.empty((h * w,), dtype=torch.int32, device=where)
+            self.arecord = torch.empty((4,), **f64)
+            self.values = torch.empty((refill * h * w * 3,), **f64)  # frame 0 lists every pixel
+        self.stride = 1 + refill  # frame k owns the passes k * stride .. (k + 1) * stride - 1
+        self.refilled = []
+        self.shown = None
+
+    def _as_var_state(self, st):
+        """A state for tray_temporal_motion_step_async: a plain one widened with a null m2."""
+        if isinstance(st, _lib.TemporalVarState):
+            return st
+        return _lib.TemporalVarState(st.colour, None, st.age, st.index, st.depth, st.width, st.height)
+
+    def frame(self, k, dev, cam, prev_cam, prev_geometry=None):
+        """Frame k through `cam` on the scene copy `dev`: the render, the step from the state of frame
+        k - 1 (seen through prev_cam; None for k = 0), the refill chain, the filter and the encoding.
+        prev_geometry: None for a scene that has not changed since frame k - 1, else (the device
+        pointer of what the scene held then, n): the step then follows the moved spheres
+        (include/tray_temporal_motion.h)."""
+        t, torch, device, stream, tp, refill = self.t, self.torch, self.device, self.stream, self.tp, self.refill
+        h, w = t.height, t.width
+        frame, states, records, var_plane = self.frame_buffer, self.states, self.records, self.var_plane
+        params = t._params(t.seed, k * self.stride)
+        dev.render_async(cam._state, params, frame.data_ptr(), None, stream)
+        out = states[k & 1]
+        history = states[(k - 1) & 1][1] if k else None
+        if prev_geometry is not None:
+            _lib.temporal_motion_step_async(dev.handle, cam._state, prev_cam._state if k else None,
+                                            prev_geometry[0] if k else None, prev_geometry[1], tp, frame.data_ptr(),
+                                            self._as_var_state(history) if k else None, self._as_var_state(out[1]),
+                                            var_plane.data_ptr() if self.variance else None, None,
+                                            records[k].data_ptr(), stream)
+        elif self.variance:
+            _lib.temporal_var_step_async(dev.handle, cam._state, prev_cam._state if k else None, tp,
+                                         frame.data_ptr(), history, out[1],
+                                         var_plane.data_ptr(), records[k].data_ptr(), stream)
+        else:
+            _lib.temporal_step_async(dev.handle, cam._state, prev_cam._state if k else None, tp,
+                                     frame.data_ptr(), history, out[1],
+                                     records[k].data_ptr(), stream)
+        if refill:
+            ast = out[1].adaptive()
+            _lib.adaptive_select_async(ast, self.ap, self.active.data_ptr(), self.arecord.data_ptr(),
+                                       self.work.data_ptr(), self.nbytes, None, device, stream)
+            n_active = int(self.arecord.cpu().numpy().view(_lib.ADAPTIVE_RECORD_DTYPE)[0]["n_active"])  # 32 bytes
+            self.refilled.append(n_active)
+            if n_active:
+                dev.render_pixels_async(cam._state, t._params(t.seed, k * self.stride + 1), self.active.data_ptr(),
+                                        n_active, self.values.data_ptr(), refill, stream=stream)
+                _lib.adaptive_fold_async(ast, self.active.data_ptr(), n_active, self.values.data_ptr(), refill, device,
+                                         stream)
+                _lib.temporal_var_variance_async(out[1], self.active.data_ptr(), n_active, var_plane.data_ptr(),
+                                                 device, stream)
+        shown = out[0]["colour"]
+        if self.denoise:
+            dev.render_aov_async(cam._state, params, *_guide_ptrs(self.aov), stream=stream)
+            if self.variance:
+                shown = t._denoise_variance_device(torch, shown, var_plane, self.aov, {})
+            else:
+                shown = t._denoise_device(torch, shown, self.aov, {})
+        _lib.linear_to_srgba_async(shown.data_ptr(), h * w, self.rgba[k].data_ptr(), device, stream)
+        self.shown = shown
+
+    def finish(self) -> list:
+        """Reads the last state, the records and the frames back into the tracer's fields; the frames."""
+        t, count, refill = self.t, self.count, self.refill
+        h, w = t.height, t.width
+        last = self.states[(count - 1) & 1][0]
+        if self.denoise:
+            t.filtered = self.shown.cpu().numpy()  # the last frame as shown, before the sRGB encoding
+        t.linear[:] = last["colour"].cpu().numpy()
+        t.age = last["age"].cpu().numpy()
+        if self.variance:
+            t.variance = self.var_plane.cpu().numpy()
+            t.m2 = last["m2"].cpu().numpy()
+            t.refilled = self.refilled if refill else [0] * count
+            t.pixel_passes = h * w * count + refill * sum(t.refilled)
+        rec = self.records.cpu().numpy()
+        t.fresh = [int(r[0]) for r in rec]
+        t.mean_age = [float(r[1]) / (h * w) for r in rec]
+        frames = [f.copy() for f in self.rgba.cpu().numpy()]
+        t.imageData[:] = frames[-1]
+        return frames
+
+
 class Tracer:  # ray/tracer.go:25-36
     """Go's Tracer embeds Camera: t.Position etc. forward to t.Camera."""
 
@@ -923,121 +1069,44 @@ class Tracer:  # ray/tracer.go:25-36
         refill that is not an integer >= 0 or exceeds max_history - 1 (a pixel could never hold
         1 + R frames), a refill_tolerance that is not finite, >= 0 and of finite square, or a
         refill_dilate other than 0 or 1, before any device work. No Go counterpart."""
-        if isinstance(refill, bool) or not isinstance(refill, (int, np.integer)) or refill < 0:
-            raise ValueError("refill must be an integer >= 0")
-        refill = int(refill)
-        if refill_dilate not in (0, 1):
-            raise ValueError("refill_dilate must be 0 or 1")
-        rt = float(refill_tolerance)
-        if not (rt >= 0.0 and rt * rt < float("inf")):
-            raise ValueError("refill_tolerance must be finite and >= 0, with a finite square")
+        refill, rt = _refill_options(refill, refill_tolerance, refill_dilate)
         variance = bool(variance) or refill > 0
         cameras = list(cameras) if cameras is not None else []
         if not cameras:
             raise ValueError("cameras must hold at least one Camera")
         if not all(isinstance(c, Camera) for c in cameras):
             raise ValueError("cameras must be a sequence of Camera objects")
-        unknown = sorted(set(overrides) - {n for n, _ in _lib.TemporalParams._fields_})
-        if unknown or "reserved" in overrides:
-            raise ValueError(f"unknown temporal parameters {unknown or ['reserved']}")
-        tp = _lib.temporal_params(**overrides)
-        if refill and tp.max_history < 1 + refill:
-            raise ValueError(f"refill={refill} needs max_history >= {1 + refill}: no pixel could hold "
-                             f"1 + refill frames (max_history is {tp.max_history})")
+        tp = _temporal_options(overrides, refill)
         scene = self._apply_defaults(scene)
         h, w = self.height, self.width
         for c in cameras:
             c.Initialize(w, h)
         object.__setattr__(self, "Camera", cameras[-1])
         self.seed = self._seed()  # once: every frame is a pass of this stream
+        self._reset_temporal_fields(variance)
+        if h * w == 0:
+            return [self.imageData.copy() for _ in cameras]
+        torch, device, where, stream = self._target()
+        dev = scene._device_scene(device)
+        loop = _TemporalLoop(self, torch, device, where, stream, len(cameras), tp, variance, refill, rt,
+                             refill_dilate, denoise)
+        for k, cam in enumerate(cameras):
+            loop.frame(k, dev, cam, cameras[k - 1] if k else None)
+        return loop.finish()
+
+    def _reset_temporal_fields(self, variance: bool) -> None:
+        """What _TemporalLoop.finish() sets, as an empty image leaves it."""
+        h, w = self.height, self.width
         self.age = np.zeros((h, w), dtype=np.int32)
         self.fresh, self.mean_age = [], []
         if variance:
             self.variance = np.full((h, w, 3), np.inf)
             self.m2 = np.zeros((h, w, 3))
             self.refilled, self.pixel_passes = [], 0
-        if h * w == 0:
-            return [self.imageData.copy() for _ in cameras]
-        torch, device, where, stream = self._target()
-        dev = scene._device_scene(device)
-        f64 = dict(dtype=torch.float64, device=where)
 
-        def planes():
-            t = dict(colour=torch.empty((h, w, 3), **f64), age=torch.empty((h, w), dtype=torch.int32, device=where),
-                     index=torch.empty((h, w), dtype=torch.int32, device=where), depth=torch.empty((h, w), **f64))
-            if variance:
-                t["m2"] = torch.empty((h, w, 3), **f64)
-                return t, _lib.TemporalVarState(t["colour"].data_ptr(), t["m2"].data_ptr(), t["age"].data_ptr(),
-                                                t["index"].data_ptr(), t["depth"].data_ptr(), w, h)
-            return t, _lib.TemporalState(t["colour"].data_ptr(), t["age"].data_ptr(), t["index"].data_ptr(),
-                                         t["depth"].data_ptr(), w, h)
-
-        states = [planes(), planes()]
-        frame = torch.empty((h, w, 3), **f64)
-        records = torch.empty((len(cameras), 2), dtype=torch.int64, device=where)
-        rgba = torch.empty((len(cameras), h, w, 4), dtype=torch.uint8, device=where)
-        aov = self._guide_buffers(torch, where) if denoise else None
-        var_plane = torch.empty((h, w, 3), **f64) if variance else None
-        if refill:
-            ap = _lib.adaptive_params(tolerance=rt, min_passes=1 + refill, max_passes=int(tp.max_history),
-                                      dilate=int(refill_dilate))
-            nbytes = _lib.adaptive_workspace_bytes(w, h)
-            work = torch.empty((nbytes // 8,), **f64)
-            active = torch.empty((h * w,), dtype=torch.int32, device=where)
-            arecord = torch.empty((4,), **f64)
-            values = torch.empty((refill * h * w * 3,), **f64)  # frame 0 lists every pixel
-        stride = 1 + refill  # frame k owns the passes k * stride .. (k + 1) * stride - 1
-        for k, cam in enumerate(cameras):
-            params = self._params(self.seed, k * stride)
-            dev.render_async(cam._state, params, frame.data_ptr(), None, stream)
-            out = states[k & 1]
-            if variance:
-                _lib.temporal_var_step_async(dev.handle, cam._state, cameras[k - 1]._state if k else None, tp,
-                                             frame.data_ptr(), states[(k - 1) & 1][1] if k else None, out[1],
-                                             var_plane.data_ptr(), records[k].data_ptr(), stream)
-            else:
-                _lib.temporal_step_async(dev.handle, cam._state, cameras[k - 1]._state if k else None, tp,
-                                         frame.data_ptr(), states[(k - 1) & 1][1] if k else None, out[1],
-                                         records[k].data_ptr(), stream)
-            if refill:
-                ast = out[1].adaptive()
-                _lib.adaptive_select_async(ast, ap, active.data_ptr(), arecord.data_ptr(), work.data_ptr(), nbytes,
-                                           None, device, stream)
-                n_active = int(arecord.cpu().numpy().view(_lib.ADAPTIVE_RECORD_DTYPE)[0]["n_active"])  # 32 bytes
-                self.refilled.append(n_active)
-                if n_active:
-                    dev.render_pixels_async(cam._state, self._params(self.seed, k * stride + 1), active.data_ptr(),
-                                            n_active, values.data_ptr(), refill, stream=stream)
-                    _lib.adaptive_fold_async(ast, active.data_ptr(), n_active, values.data_ptr(), refill, device,
-                                             stream)
-                    _lib.temporal_var_variance_async(out[1], active.data_ptr(), n_active, var_plane.data_ptr(),
-                                                     device, stream)
-            shown = out[0]["colour"]
-            if denoise:
-                dev.render_aov_async(cam._state, params, *_guide_ptrs(aov), stream=stream)
-                if variance:
-                    shown = self._denoise_variance_device(torch, shown, var_plane, aov, {})
-                else:
-                    shown = self._denoise_device(torch, shown, aov, {})
-            _lib.linear_to_srgba_async(shown.data_ptr(), h * w, rgba[k].data_ptr(), device, stream)
-        last = states[(len(cameras) - 1) & 1][0]
-        if denoise:
-            self.filtered = shown.cpu().numpy()  # the last frame as shown, before the sRGB encoding
-        self.linear[:] = last["colour"].cpu().numpy()
-        self.age = last["age"].cpu().numpy()
-        if variance:
-            self.variance = var_plane.cpu().numpy()
-            self.m2 = last["m2"].cpu().numpy()
-            self.refilled = self.refilled if refill else [0] * len(cameras)
-            self.pixel_passes = h * w * len(cameras) + refill * sum(self.refilled)
-        rec = records.cpu().numpy()
-        self.fresh = [int(r[0]) for r in rec]
-        self.mean_age = [float(r[1]) / (h * w) for r in rec]
-        frames = [f.copy() for f in rgba.cpu().numpy()]
-        self.imageData[:] = frames[-1]
-        return frames
-
-    def RenderAnimation(self, scene: Scene | None, geometries, denoise: bool = False) -> list:
+    def RenderAnimation(self, scene: Scene | None, geometries, denoise: bool = False, temporal: bool = False,
+                        variance: bool = False, refill: int = 0, refill_tolerance: float = 1e150,
+                        refill_dilate: int = 1, cameras=None, **overrides) -> list:
         """Moving spheres under the tracer's camera (include/tray_scene_update.h): frame k shows the
         scene with its spheres at geometries[k], a (k, n, 4) float64 array or device tensor of
         {cx, cy, cz, radius} per sphere in list order, as progressive pass k of the tracer's one
@@ -1052,9 +1121,41 @@ class Tracer:  # ray/tracer.go:25-36
         then made by a release and a fresh upload of its geometry, and the frames after it again by
         updates of the new copy. Every frame has the bits of a fresh upload's render either way.
 
+        temporal=True (include/tray_temporal_motion.h) keeps what the frames before have seen: frame k
+        is update, render, tray_temporal_motion_step_async with geometries[k - 1] as the previous
+        geometry (the tensor where it is), the optional refill chain, the optional filter and the
+        encoding, on one stream over two ping-pong states: the history follows each hit point with
+        its sphere. variance, refill, refill_tolerance, refill_dilate and the overrides (fields of
+        tray_temporal_params) mean what they mean in RenderSequence, and `age`, `fresh`, `mean_age`,
+        `variance`, `m2`, `refilled`, `pixel_passes` and `filtered` are set as there; `linear` is the
+        last accumulated frame. The 32-byte update record of frame k is then read before frame k is
+        rendered (one small readback per frame, as the refill chain has): on a refusal the scene is
+        released and uploaded afresh with geometries[k] at once, and the history carries over
+        unchanged, since the step takes the previous geometry as a buffer and sphere order is the
+        list order either way. History follows surfaces, not light: what a moved neighbour changes
+        in a static surface's shading arrives with the lag of max_history (the header, section 5).
+
+        cameras: an optional sequence of k Cameras, frame k through cameras[k] (each initialized
+        here); the tracer's camera for every frame by default. Without temporal they only replace
+        the camera per frame.
+
         Returns the list of (H, W, 4) uint8 RGBA frames and keeps the last in imageData and, before
         the encoding, in `linear`; the scene's Objects end at the last geometry. ValueError for an
-        empty sequence or a shape other than (k, n, 4), before any device work. No Go counterpart."""
+        empty sequence or a shape other than (k, n, 4), for cameras whose length is not k or that
+        hold anything but Cameras, for variance, refill, their two options or an override without
+        temporal=True, and with it for what RenderSequence refuses, before any device work. No Go
+        counterpart."""
+        if not temporal and (variance or refill or overrides or refill_tolerance != 1e150 or refill_dilate != 1):
+            raise ValueError("variance, refill, refill_tolerance, refill_dilate and temporal parameters need "
+                             "temporal=True")
+        if temporal:
+            refill, rt = _refill_options(refill, refill_tolerance, refill_dilate)
+            variance = bool(variance) or refill > 0
+            tp = _temporal_options(overrides, refill)
+        if cameras is not None:
+            cameras = list(cameras)
+            if not all(isinstance(c, Camera) for c in cameras):
+                raise ValueError("cameras must be a sequence of Camera objects")
         scene = self._apply_defaults(scene)
         self.Camera.Initialize(self.width, self.height)
         import torch
@@ -1068,13 +1169,43 @@ class Tracer:  # ray/tracer.go:25-36
         if on_device and geometries.dtype != torch.float64:
             raise ValueError("geometries must be float64")
         count = int(geometries.shape[0])
+        if cameras is not None:
+            if len(cameras) != count:
+                raise ValueError(f"cameras must hold one Camera per frame ({count}); got {len(cameras)}")
+            for c in cameras:
+                c.Initialize(w, h)
+            object.__setattr__(self, "Camera", cameras[-1])
+        else:
+            cameras = [self.Camera] * count
         self.seed = self._seed()  # once: every frame is a pass of this stream
         self.applied = []
+        if temporal:
+            self._reset_temporal_fields(variance)
         if h * w == 0:
             return [self.imageData.copy() for _ in range(count)]
         torch, device, where, stream = self._target()
         geo = geometries.to(where).contiguous() if on_device else torch.from_numpy(geometries).to(where)
         dev = scene._device_scene(device)
+        if temporal:
+            loop = _TemporalLoop(self, torch, device, where, stream, count, tp, variance, refill, rt, refill_dilate,
+                                 denoise)
+            record = torch.zeros((_lib.SCENE_UPDATE_RECORD_DTYPE.itemsize // 8,), dtype=torch.float64, device=where)
+            for k in range(count):
+                applied = 1
+                if n:
+                    dev.update_async(geo[k].data_ptr(), n, record.data_ptr(), stream)
+                    applied = int(record.cpu().numpy().view(_lib.SCENE_UPDATE_RECORD_DTYPE)[0]["applied"])  # 32 bytes
+                    if not applied:  # refused: this geometry as a fresh upload; the history stays
+                        scene._set_geometry(geo[k].cpu().numpy())
+                        dev.release()
+                        scene._adopt(device, None)
+                        dev = scene._device_scene(device)
+                self.applied.append(applied)
+                loop.frame(k, dev, cameras[k], cameras[k - 1] if k else None,
+                           (geo[k - 1].data_ptr() if k and n else None, n))
+            scene._set_geometry(geo[count - 1].cpu().numpy())
+            scene._adopt(device, dev)
+            return loop.finish()
         records = torch.zeros((count, _lib.SCENE_UPDATE_RECORD_DTYPE.itemsize // 8), dtype=torch.float64, device=where)
         rgba = torch.empty((count, h, w, 4), dtype=torch.uint8, device=where)
         colour = torch.empty((h, w, 3), dtype=torch.float64, device=where)
@@ -1085,10 +1216,10 @@ class Tracer:  # ray/tracer.go:25-36
                 if n and not (uploaded and k == start):
                     dev.update_async(geo[k].data_ptr(), n, records[k].data_ptr(), stream)
                 params = self._params(self.seed, k)
-                dev.render_async(self.Camera._state, params, colour.data_ptr(), None, stream)
+                dev.render_async(cameras[k]._state, params, colour.data_ptr(), None, stream)
                 shown = colour
                 if denoise:
-                    dev.render_aov_async(self.Camera._state, params, *_guide_ptrs(aov), stream=stream)
+                    dev.render_aov_async(cameras[k]._state, params, *_guide_ptrs(aov), stream=stream)
                     shown = self._denoise_device(torch, colour, aov, {})
                 _lib.linear_to_srgba_async(shown.data_ptr(), h * w, rgba[k].data_ptr(), device, stream)
             flags = records.cpu().numpy().reshape(-1).view(_lib.SCENE_UPDATE_RECORD_DTYPE)["applied"]
