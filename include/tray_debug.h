@@ -88,6 +88,12 @@ int tray_debug_plain_instance(uint32_t facts, int32_t rays_per_pixel, int32_t ti
                               int32_t *plain_out);
 /* Launches (one per band) that took the plain-frame instance since the library was loaded. */
 int tray_debug_plain_launches(uint64_t *count_out);
+/* The plain-frame instance's batch trigger (phase_fires of tray_amd/csrc/tray_kernel.hpp, the very
+ * function the kernel compiles): whether phase `phase` (0 leaf, 1 shade, 2 refill) runs with
+ * `waiting` lanes gathered for it while `traversing` lanes are in flight, each 0..64. The generic
+ * instances keep their fixed lane counts, so the "plain_instance" knob at 0 is also the switch back
+ * to that schedule (same bits). Host only: no device is touched. */
+int tray_debug_phase_trigger(int32_t phase, uint32_t waiting, uint32_t traversing, int32_t *fires_out);
 
 /* The kernel families that find their hits outside the megakernel, for tray_debug_query_traversal. */
 #define TRAY_QUERY_KIND_PLAIN 0    /* tray_scene_hit_async, tray_scene_occluded_async, tray_ray_color_async,

@@ -409,8 +409,10 @@ assert NODE_DTYPE.itemsize == 128
 
 # include/tray_debug.h: test / A-B hooks outside the stable ABI (not in EXPORTS).
 DEBUG_EXPORTS = ("tray_debug_set", "tray_debug_clear", "tray_debug_progress_counts", "tray_debug_plain_instance",
-                 "tray_debug_plain_launches", "tray_debug_query_traversal", "tray_debug_scene_nodes",
-                 "tray_debug_scene_leaves")
+                 "tray_debug_plain_launches", "tray_debug_phase_trigger", "tray_debug_query_traversal",
+                 "tray_debug_scene_nodes", "tray_debug_scene_leaves")
+# tray_debug_phase_trigger's phases.
+TRIGGER_PHASES = {"leaf": 0, "shade": 1, "refill": 2}
 DEBUG_KNOBS = ("acc_slots", "band_samples", "bvh_leaf", "bvh_lds_mode", "stack_lds_slots", "node_deep",
                "primary_candidates", "resolve_staged", "wave_chunks", "scene_contexts", "grid_reserve",
                "work_order", "coop_lanes", "plain_instance")
@@ -570,6 +572,8 @@ def lib(path: str | None = None) -> ctypes.CDLL:
     if hasattr(L, "tray_debug_plain_instance"):  # absent from older builds (A/B tools)
         L.tray_debug_plain_instance.argtypes = [ctypes.c_uint32] + [i32] * 7 + [ctypes.POINTER(i32)]
         L.tray_debug_plain_launches.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(L, "tray_debug_phase_trigger"):  # absent from older builds (A/B tools)
+        L.tray_debug_phase_trigger.argtypes = [i32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(i32)]
     if hasattr(L, "tray_debug_query_traversal"):  # absent from older builds (A/B tools)
         L.tray_debug_query_traversal.argtypes = [i32, i32, ctypes.POINTER(i32)]
     _libs[path] = L
@@ -636,6 +640,14 @@ def plain_launches() -> int:
     n = ctypes.c_uint64(0)
     check(lib().tray_debug_plain_launches(ctypes.byref(n)))
     return int(n.value)
+
+
+def phase_trigger(phase: str, waiting: int, traversing: int) -> bool:
+    """tray_debug_phase_trigger: whether the plain-frame instance runs `phase` (a name of
+    TRIGGER_PHASES) with `waiting` lanes gathered and `traversing` lanes in flight. Host only."""
+    out = ctypes.c_int32(-1)
+    check(lib().tray_debug_phase_trigger(TRIGGER_PHASES[phase], waiting, traversing, ctypes.byref(out)))
+    return out.value == 1
 
 
 def query_traversal(kind: str, stack_depth: int) -> bool:

@@ -364,6 +364,14 @@ int tray_debug_plain_launches(uint64_t* count_out) {
     return TRAY_OK;
 }
 
+int tray_debug_phase_trigger(int32_t phase, uint32_t waiting, uint32_t traversing, int32_t* fires_out) {
+    if (!fires_out) return fail(TRAY_ERR_INVALID_ARGUMENT, "null argument");
+    if (phase < kPhaseLeaf || phase > kPhaseRefill || waiting > 64u || traversing > 64u)
+        return fail(TRAY_ERR_INVALID_ARGUMENT, "phase 0..2, lanes 0..64");
+    *fires_out = phase_fires(waiting, traversing, phase_cost(phase)) ? 1 : 0;
+    return TRAY_OK;
+}
+
 const char* tray_last_error(void) { return g_last_error.c_str(); }
 
 int tray_device_count(int32_t* count) {

@@ -168,6 +168,19 @@ struct PlainFrame {
     static constexpr bool kNoSegments = true, kNoCount = true, kCand = true, kMultiSample = true, kContigRows = true,
                           kOrdered = true, kOneGlobal = true, kHasNodes = true, kSingleLeaf = true;
 };
+// Not a fact of the launch but the schedule measured for an instance: whether its leaf,
+// shade and refill phases run by the cost rule (phase_fires, tray_kernel.hpp) or by the fixed lane
+// counts. The plain-frame instance was measured; the generic instances keep their counts and code.
+#ifdef TRAY_TRIGGERS_ALL  // the profile's build only: the stats instance is a generic one. Every instance then
+                          // takes the rule, the linear scan's refill too (its busy lanes are its lanes in flight).
+template <class Opt>
+inline constexpr bool kCostTriggers = true;
+#else
+template <class Opt>
+inline constexpr bool kCostTriggers = false;
+template <>
+inline constexpr bool kCostTriggers<PlainFrame> = true;
+#endif
 
 // The draw block of (pixel, sample, bounce, purpose) (include/tray.h, rng.hpp draw_block).
 __device__ __forceinline__ Block draw(const KernelParams& p, uint32_t pixel, uint32_t sample, uint32_t bounce,

@@ -20,6 +20,8 @@
 //     with -DTRAY_PROFILE_REFILL                   --refill-split           slots 10, 13-15: the refill's parts
 //     with -DTRAY_PROFILE_CANDWAIT                                          slot 15: the candidate record's wait
 //     with -DTRAY_PROFILE_MATERIAL                 --material               prof_material, behind the stamps
+//     with -DTRAY_TRIGGERS_ALL                                              the stats instance (a generic one) runs the
+//                                                                           plain-frame instance's cost-rule triggers
 //   -DTRAY_PROFILE_TIMELINE                      tools/timeline.py          a record per wave from stats[32]
 //   -DTRAY_STATS_PRIMARY                         tools/primary_share.py     Stats fields, stats[3..7]
 //   -DTRAY_STATS_GROUND                          tools/ground_share.py      Stats fields, stats[3..10]

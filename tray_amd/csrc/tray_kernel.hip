@@ -787,6 +787,23 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
 #endif
     constexpr uint32_t kNoRun = 0x80000000u;
     uint32_t run_first = kNoRun;
+    // Which batch triggers follow the cost rule (phase_fires, tray_kernel.hpp) in this instance; the
+    // A/B switches restore each old test.
+#ifdef TRAY_AB_FIXED_REFILL
+    constexpr bool kRuleRefill = false;
+#else
+    constexpr bool kRuleRefill = kCostTriggers<kOpt>;
+#endif
+#ifdef TRAY_AB_FIXED_LEAF
+    constexpr bool kRuleLeaf = false;
+#else
+    constexpr bool kRuleLeaf = kCostTriggers<kOpt>;
+#endif
+#ifdef TRAY_AB_FIXED_SHADE
+    constexpr bool kRuleShade = false;
+#else
+    constexpr bool kRuleShade = kCostTriggers<kOpt>;
+#endif
     bool exhausted = false;
     int32_t prog_cur = 0;  // live progress: the wave's current tile row and its unflushed count
     uint64_t prog_cnt = 0;
@@ -801,7 +818,11 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
         if constexpr (Diag::kPhase<kStats>) dg.phase_begin<kStats>();
         TRAY_MARK("refill_assign")
         uint64_t idle = __ballot(!L.busy);
-        if (__popcll(idle) < TRAY_REFILL_BATCH && idle != ~0ull) idle = 0ull;  // batch refills
+        // Batch refills: by the cost rule against the busy lanes (kCostTriggers; idle + busy = 64, so a
+        // count again: 21 idle lanes at the plain instance's cost of 10), or from the fixed count.
+        if (kRuleRefill ? !phase_fires((uint32_t)__popcll(idle), 64u - (uint32_t)__popcll(idle), phase_cost(kPhaseRefill))
+                        : __popcll(idle) < TRAY_REFILL_BATCH && idle != ~0ull)
+            idle = 0ull;
         // Items are assigned first (cheap, may span two chunks); the camera rays of
         // all newly assigned lanes are then generated together.
         // A lane's item and its copy of the chunk's values go straight into its Lane fields, dead
@@ -1164,8 +1185,9 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             // Leaf phase: FP64 sphere tests, batched.
             const uint64_t m_leaf = __ballot(is_leaf(T.cur));
             const uint32_t n_trav = (uint32_t)__popcll(__ballot(is_trav(T.cur)));
-            if (m_leaf != 0ull && (__popcll(m_leaf) >= TRAY_LEAF_BATCH || n_trav == 0u ||
-                                   (n_trav < TRAY_TRAV_SPARSE && __popcll(m_leaf) >= TRAY_LEAF_LOW))) {
+            if (kRuleLeaf ? phase_fires((uint32_t)__popcll(m_leaf), n_trav, phase_cost(kPhaseLeaf))
+                          : m_leaf != 0ull && (__popcll(m_leaf) >= TRAY_LEAF_BATCH || n_trav == 0u ||
+                                               (n_trav < TRAY_TRAV_SPARSE && __popcll(m_leaf) >= TRAY_LEAF_LOW))) {
                 if constexpr (Diag::kPhase<kStats>) dg.phase_begin<kStats>();
                 TRAY_MARK("leaf_ctl")
                 if constexpr (Diag::kLeafPhase) dg.leaf_phase(lane, m_leaf);
@@ -1183,9 +1205,12 @@ __global__ __launch_bounds__(kBVH ? kBvhBlock : 256, kBVH ? TRAY_BVH_WAVES_PER_S
             }
             // Shading phase, batched.
             const uint64_t m_shade = __ballot(L.busy && T.cur == kBvhNone);
-            if (m_shade != 0ull && (__popcll(m_shade) >= TRAY_SHADE_BATCH || __ballot(T.cur < kBvhNone) == 0ull ||
-                                    (__popcll(__ballot(is_trav(T.cur))) < TRAY_TRAV_SPARSE &&
-                                     __popcll(m_shade) >= TRAY_SHADE_LOW))) {
+            // (the rule's lanes in flight: those traversing and those waiting for the leaf phase)
+            if (kRuleShade ? phase_fires((uint32_t)__popcll(m_shade), (uint32_t)__popcll(__ballot(T.cur < kBvhNone)),
+                                         phase_cost(kPhaseShade))
+                           : m_shade != 0ull && (__popcll(m_shade) >= TRAY_SHADE_BATCH || __ballot(T.cur < kBvhNone) == 0ull ||
+                                                 (__popcll(__ballot(is_trav(T.cur))) < TRAY_TRAV_SPARSE &&
+                                                  __popcll(m_shade) >= TRAY_SHADE_LOW))) {
                 if constexpr (Diag::kPhase<kStats>) dg.phase_begin<kStats>();
                 TRAY_MARK("shade_ctl")
                 if constexpr (Diag::kShadePhase) dg.shade_phase(lane, m_shade);

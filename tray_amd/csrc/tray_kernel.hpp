@@ -157,6 +157,40 @@ struct KernelParams {
     uint32_t wild_att;
 };
 
+// The batch trigger of a megakernel phase (leaf, shade, refill; render_kernel). A pass
+// of a phase costs the wave the same for 1 lane or 64, so lanes wait for it in a batch, and while
+// they wait they sit empty through the node steps of the lanes still traversing. `waiting` lanes
+// have gathered; the `traversing` lanes send new ones at a rate proportional to their number, so a
+// batch as large again takes waiting / traversing x (node steps between a lane's visits to the
+// phase) more node steps. The pass runs once the lanes times those steps reach its cost:
+// waiting^2 >= traversing x cost, `cost` = 2 x 64 x (cycles per pass / cycles per node step) /
+// (node steps between visits), the batch size that minimises pass cost plus empty lanes per node
+// step. With nothing traversing any waiting lane runs the pass (nothing else can make progress: the
+// drain and the all-padding refill rely on it), and no pass runs for no lane.
+__host__ __device__ constexpr bool phase_fires(uint32_t waiting, uint32_t traversing, uint32_t cost) {
+    return waiting != 0u && waiting * waiting >= traversing * cost;
+}
+// The phases' costs for the plain-frame instance. The formula above with the cycles of
+// profiles/r16_phase_c2_parent.json gives 20 (leaf), 152 (shade, with the scatter and begin steps its
+// hits bring on) and 87 (refill): upper ends, since a waiting lane also sits through the other
+// phases' passes, not only through node steps (37 % of the cycles). Swept downwards from there on C2
+// (profiles/r16_ab_triggers_sweep{1,2}_c2_p{1,16}.jsonl): the leaf cost is flat from 5 to 14, the
+// shade cost best at 100 (50 / 70 / 141 / 200 lose 1.2 / 0.4 / 0.3 / 0.7 %), the refill cost at 8-10
+// (4 / 6 / 19 / 40 lose 0.7 / 0.3 / 1.1 / 5 %). The macros are how that sweep's builds set a cost.
+#ifndef TRAY_TRIGGER_LEAF
+#define TRAY_TRIGGER_LEAF 7
+#endif
+#ifndef TRAY_TRIGGER_SHADE
+#define TRAY_TRIGGER_SHADE 100
+#endif
+#ifndef TRAY_TRIGGER_REFILL
+#define TRAY_TRIGGER_REFILL 10
+#endif
+enum : int32_t { kPhaseLeaf = 0, kPhaseShade = 1, kPhaseRefill = 2 };
+__host__ __device__ constexpr uint32_t phase_cost(int32_t phase) {
+    return phase == kPhaseLeaf ? TRAY_TRIGGER_LEAF : phase == kPhaseShade ? TRAY_TRIGGER_SHADE : TRAY_TRIGGER_REFILL;
+}
+
 struct LaunchPlan;
 // Enqueues the render of `plan` (plan_launch of the same p and use_bvh): the
 // megakernel and resolve pass of every band. `samples_bytes` is the capacity
